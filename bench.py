@@ -10,7 +10,7 @@ tree) over one synthetic batch of trace columns, inputs already resident in HBM:
              RCCL all-gather of digests/cap.
 value = W * N_total / t / 1e9 (GFE/s, whole job).  One JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--width 135] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--width 135] [--no-cpu-baseline] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -135,6 +135,45 @@ def golden(name):
         return json.load(open(os.environ.get("P2HOT_BENCH_GOLDEN_CAPS") or os.path.join(ROOT, "tests", "golden", "commit_caps.json")))[name]
     except Exception:
         return None
+
+
+DUMP_SAMPLE = 1 << 19     # field elements kept of an array larger than this (--dump-outputs)
+DUMP_SEED = 20260101
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(eng, outputs, directory):
+    """--dump-outputs DIR: the arrays the timed step returned to its caller (ShardedCommit.run) as DIR/<name>.npy, so that two
+    builds can be compared output for output.  A u64 field element does not fit a float64, so each one is stored exactly as its
+    two 32-bit halves: a trailing axis of 2, [..., 0] = low word, [..., 1] = high word.  An array of more than DUMP_SAMPLE
+    elements is sampled at fixed seeded flat indices (the same for the same shape), written beside it as DIR/<name>_index.npy.
+    Returns {name: {"shape", "sampled"}} for the JSON line."""
+    os.makedirs(directory, exist_ok=True)
+    written, total = {}, 0
+    for name in sorted(outputs):
+        buf = outputs[name]
+        if buf is None:
+            continue
+        shape, numel = list(buf.shape), int(np.prod(buf.shape, dtype=np.int64))
+        idx = None
+        if numel > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(numel, DUMP_SAMPLE, replace=False))
+            if hasattr(buf, "index_select"):  # device tensor: gather the sample on the device, copy only that
+                import torch
+                vals = eng.host(buf.reshape(-1).index_select(0, torch.from_numpy(idx.astype(np.int64)).to(buf.device)))
+            else:
+                vals = eng.host(buf).reshape(-1)[idx]
+        else:
+            vals = eng.host(buf).reshape(shape)
+        vals = np.stack([vals & np.uint64(0xFFFFFFFF), vals >> np.uint64(32)], axis=-1).astype(np.float64)
+        np.save(os.path.join(directory, name + ".npy"), vals)
+        total += vals.nbytes
+        if idx is not None:
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            total += idx.size * 8
+        written[name] = {"shape": shape, "sampled": None if idx is None else int(idx.size)}
+    assert total <= DUMP_BUDGET_BYTES, "--dump-outputs wrote %d bytes" % total
+    return written
 
 
 def host_pointer_lines(eng, out, reps):
@@ -786,7 +825,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra driver-timed lines of the other BASELINE shapes")
     ap.add_argument("--extra-only", default=None, help="tooling: only this group of extra lines (host)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (coefficients, LDE, digests, cap) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves (one process per GPU under
     # torch.distributed.run, rendezvous on 127.0.0.1), pass the child's JSON line and exit code through
@@ -942,11 +985,12 @@ def main():
         """W untimed warm-up steps, then exactly K steps between barrier + device synchronisation on both sides; the cap of EVERY
         timed step is kept (512 bytes each, an asynchronous device copy) and compared, after the timed region, with the oracle's
         golden cap of the same synthetic columns (tests/golden/commit_caps.json: the headline shape and the 2 / 4 / 8-GPU
-        weak-scaling shapes, C5 at 8).  Returns (seconds, kernel profile, cap_checked, golden record)."""
+        weak-scaling shapes, C5 at 8).  Returns (seconds, kernel profile, cap_checked, golden record, the last step's outputs)."""
         cap_log = eng.mem.zeros(max(args.steps, 1), (1 << cap) * 4)
+        last = {}
 
         def step(i=None):
-            job.run(cols)
+            last["outputs"] = job.run(cols)
             if i is not None:
                 if emu:
                     cap_log[i][...] = eng.host(job.cap).reshape(-1)
@@ -979,7 +1023,7 @@ def main():
             cap_checked = not bad and args.steps > 0
             if bad:
                 raise SystemExit("bench: the Merkle cap of timed step(s) %s differs from the oracle's golden cap" % bad[:8])
-        return dt, prof, cap_checked, g
+        return dt, prof, cap_checked, g, last["outputs"]
 
     def max_over_ranks(dt):
         if not dist:
@@ -988,7 +1032,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    dt, prof, cap_checked, g = timed_steps(job, cols, log_n)
+    dt, prof, cap_checked, g, outputs = timed_steps(job, cols, log_n)
+    dumped = dump_outputs(eng, outputs, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
+    del outputs
     rank_rows = None
     if dist:
         dt_local, dt = dt, max_over_ranks(dt)
@@ -1012,13 +1058,13 @@ def main():
         except ValueError as ex:
             strong, job2 = {"scaling": "strong", "skipped": str(ex)}, None
         if job2 is not None:
-            dt2, _prof2, cap2, _g2 = timed_steps(job2, cols2, args.log_n)
+            dt2, _prof2, cap2, _g2, out2 = timed_steps(job2, cols2, args.log_n)
             dt2 = max_over_ranks(dt2)
             strong = {"scaling": "strong", "workload": "PolynomialBatch::from_values, W=%d, 2^%d rows IN TOTAL split over %d ranks, rate 1/%d, cap_height %d"
                                                        % (W, args.log_n, world, 1 << rb, cap),
                       "ms_per_step": dt2 / args.steps * 1e3, "value": W * (1 << (args.log_n + rb)) / (dt2 / args.steps) / 1e9, "unit": "GFE/s",
                       "steps": args.steps, "cap_checked": cap2, "caps_checked": args.steps if cap2 else 0}
-            del job2, cols2
+            del job2, cols2, out2
 
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -1071,6 +1117,7 @@ def main():
             "kernels": kern,
             "algorithmic_bytes_per_step": ab,
             "commit_hbm_frac": ab["total"] / world / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+            **({"dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {}),
         }
         if world == 1 and not args.no_extra and not emu:
             del job, cols

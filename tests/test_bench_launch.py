@@ -115,3 +115,23 @@ def test_a_wrong_cap_fails_the_bench(tmp_path):
                env_extra={"P2HOT_BENCH_GOLDEN_CAPS": str(alt)})
     assert r.returncode != 0 and "differs from the oracle's golden cap" in (r.stderr + r.stdout)
     shutil.rmtree(tmp_path, ignore_errors=True)
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the arrays of the last timed step as float64 .npy (u64 field elements as [low, high] 32-bit halves), the
+    cap equal to the oracle's golden; --steps sets the number of timed steps and the line carries ms_per_step"""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "7", "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_json_line(r.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["caps_checked"] == 3
+    assert set(d["dumped_outputs"]["arrays"]) == {"cap", "coeffs", "digests", "lde"}
+    arrays = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(arrays) == {"cap", "coeffs", "digests", "lde"} and all(a.dtype == np.float64 for a in arrays.values())
+    assert arrays["coeffs"].shape == (135, 1 << 7, 2) and arrays["lde"].shape == (135, 1 << 10, 2)
+    halves = arrays["cap"].astype(np.uint64)
+    assert ((halves[..., 1] << np.uint64(32)) | halves[..., 0]).tolist() == json.load(open(os.path.join(ROOT, "tests", "golden", "commit_caps.json")))["tiny_wires"]["cap"]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+    r = _bench("--gpus", "1", "--steps", "0", "--log-n", "7", "--no-extra", "--no-cpu-baseline")
+    assert r.returncode != 0 and "--steps" in r.stderr
