@@ -112,6 +112,19 @@ int p2hot_poseidon_permute_dev(p2hot_ctx *ctx, uint64_t *d_states, size_t count)
 int p2hot_merkle_dev(p2hot_ctx *ctx, const uint64_t *d_leaves, int layout, size_t leaf_stride, size_t W,
                      unsigned log_leaves, unsigned cap_height, size_t leaf_begin, size_t leaf_count,
                      uint64_t *d_digests, uint64_t *d_cap);
+/* ---------------------------------------------------------------- KeccakHash<N> (hash/keccak.rs:104-127)
+ * Keccak-256 trees for KeccakGoldilocksConfig (plonk/config.rs:118-126).  A KeccakHash<N> digest (N = hash_size, 1..32 bytes;
+ * 0 or > 32 is P2HOT_EINVAL) occupies bytes 0..N of the same 4-word slot a Poseidon digest does, bytes N..32 zero, so the
+ * digest / cap arrays, p2hot_merkle_paths_dev and p2hot_batch_paths / _digests carry Keccak trees unchanged.
+ * p2hot_keccak256_dev: `count` messages of msg_bytes bytes, back to back in d_msgs; d_out [count][4] the 32-byte output of the
+ * sponge with rate 136 and the given domain byte (0x01 = Keccak-256 as keccak_hash::keccak, 0x06 = SHA3-256). */
+int p2hot_keccak256_dev(p2hot_ctx *ctx, const uint8_t *d_msgs, size_t msg_bytes, size_t count, unsigned domain_byte,
+                        uint64_t *d_out);
+/* p2hot_merkle_dev for KeccakHash<hash_size>: MerkleTree::new with hash_or_noop on the leaves (plonk/config.rs:63-74: a leaf
+ * of 8 * W <= hash_size bytes is its canonical bytes, zero-padded) and two_to_one = Keccak-256(left[0..N] || right[0..N]) */
+int p2hot_keccak_merkle_dev(p2hot_ctx *ctx, const uint64_t *d_leaves, int layout, size_t leaf_stride, size_t W,
+                            unsigned log_leaves, unsigned cap_height, size_t leaf_begin, size_t leaf_count,
+                            uint64_t *d_digests, uint64_t *d_cap, unsigned hash_size);
 /* Field-arithmetic self test (goldilocks_field.rs:245-320, :402-415): for count operand pairs writes six arrays of
  * `count` words to d_out: a*b by the compiler-scheduled multiply, by the hand-scheduled single stream, by the 3-way
  * interleaved stream, a+b, a-b (all canonical), and a word that is 0 unless a hand-written instruction stream disagreed
@@ -140,6 +153,12 @@ int p2hot_commit_dev(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_stride, 
                      unsigned rate_bits, unsigned cap_height, int is_values, size_t row_begin, size_t row_count,
                      uint64_t *d_coeffs, size_t coeff_stride, uint64_t *d_lde, size_t lde_stride,
                      uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap);
+
+/* p2hot_commit_dev with the tree built by KeccakHash<hash_size> (the LDE does not depend on the hasher) */
+int p2hot_commit_keccak_dev(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_stride, size_t W, unsigned log_n,
+                            unsigned rate_bits, unsigned cap_height, int is_values, size_t row_begin, size_t row_count,
+                            uint64_t *d_coeffs, size_t coeff_stride, uint64_t *d_lde, size_t lde_stride,
+                            uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, unsigned hash_size);
 
 /* ---------------------------------------------------------------- Challenger (device-resident) */
 /* plonky2/src/iop/challenger.rs:16-153.  The sponge lives on the GPU so FRI rounds need no host
@@ -266,6 +285,12 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * P2HOT_LEAVES_ASYNC blocks arrive in -- and MerkleTree::get(r) is row reverse_bits(r).  p2hot_batch_rows / _paths and the proofs keep
  * the committed indexing: only the host copy's row order changes. */
 #define P2HOT_LEAVES_NATURAL 8u
+/* p2hot_commit / _salted / _cols: the Merkle tree's hasher in bits 8..15 of the flag word.  0 = PoseidonHash; n = 1..32 =
+ * KeccakHash<n> (digests in 32-byte slots, see p2hot_keccak_merkle_dev); 33..255 is P2HOT_EINVAL.  The batch records its hasher:
+ * p2hot_prove_openings / _many refuse a Keccak batch with P2HOT_EUNSUPPORTED (FRI for the Keccak config stays on the CPU);
+ * p2hot_batch_rows / _paths / _digests / _coeffs, p2hot_eval_openings and p2hot_quotient_polys do not depend on the hasher. */
+#define P2HOT_HASH_KECCAK(n) ((unsigned)(n) << 8)
+#define P2HOT_HASH_MASK 0xFF00u
 
 typedef struct p2hot_batch p2hot_batch;
 typedef struct p2hot_cols p2hot_cols;

@@ -59,13 +59,14 @@ use crate::fri::structure::FriInstanceInfo;
 use crate::fri::FriParams;
 use crate::hash::hash_types::RichField;
 use crate::hash::hashing::PlonkyPermutation;
+use crate::hash::keccak::KeccakHash;
 use crate::hash::merkle_proofs::MerkleProof;
 use crate::hash::merkle_tree::{MerkleCap, MerkleTree};
 use crate::hash::poseidon::PoseidonHash;
 use crate::iop::challenger::Challenger;
 use crate::iop::witness::MatrixWitness;
 use crate::plonk::circuit_data::{CommonCircuitData, ProverOnlyCircuitData};
-use crate::plonk::config::{GenericConfig, Hasher};
+use crate::plonk::config::{GenericConfig, GenericHashOut, Hasher};
 use crate::plonk::plonk_common::reduce_with_powers_multi;
 use crate::plonk::vanishing_poly::evaluate_gate_constraints_base_batch;
 use crate::plonk::vars::EvaluationVarsBaseBatch;
@@ -172,6 +173,10 @@ pub const P2HOT_KEEP_VALUES: c_uint = 1;
 pub const P2HOT_COEFFS_PER_COLUMN: c_uint = 2;
 pub const P2HOT_LEAVES_ASYNC: c_uint = 4;
 pub const P2HOT_LEAVES_NATURAL: c_uint = 8;
+/// P2HOT_HASH_KECCAK(n): the commitment's tree is built with KeccakHash<n> (flag bits 8..15; 0 = PoseidonHash)
+pub const fn hash_keccak_flag(n: usize) -> c_uint {
+    (n as c_uint) << 8
+}
 
 #[link(name = "p2hot")]
 extern "C" {
@@ -205,6 +210,11 @@ extern "C" {
         ctx: *mut P2hotCtx, d_leaves: *const u64, layout: c_int, leaf_stride: usize, W: usize, log_leaves: c_uint, cap_height: c_uint,
         leaf_begin: usize, leaf_count: usize, d_digests: *mut u64, d_cap: *mut u64,
     ) -> c_int;
+    pub fn p2hot_keccak256_dev(ctx: *mut P2hotCtx, d_msgs: *const u8, msg_bytes: usize, count: usize, domain_byte: c_uint, d_out: *mut u64) -> c_int;
+    pub fn p2hot_keccak_merkle_dev(
+        ctx: *mut P2hotCtx, d_leaves: *const u64, layout: c_int, leaf_stride: usize, W: usize, log_leaves: c_uint, cap_height: c_uint,
+        leaf_begin: usize, leaf_count: usize, d_digests: *mut u64, d_cap: *mut u64, hash_size: c_uint,
+    ) -> c_int;
     pub fn p2hot_field_selftest_dev(ctx: *mut P2hotCtx, d_a: *const u64, d_b: *const u64, count: usize, d_out: *mut u64) -> c_int;
     pub fn p2hot_gather_rows_dev(
         ctx: *mut P2hotCtx, d_colmajor: *const u64, col_stride: usize, rows: usize, W: usize, d_idx: *const u64, m: usize, d_out: *mut u64,
@@ -213,6 +223,11 @@ extern "C" {
         ctx: *mut P2hotCtx, d_cols: *const u64, col_stride: usize, W: usize, log_n: c_uint, rate_bits: c_uint, cap_height: c_uint,
         is_values: c_int, row_begin: usize, row_count: usize, d_coeffs: *mut u64, coeff_stride: usize, d_lde: *mut u64, lde_stride: usize,
         d_leaves: *mut u64, d_digests: *mut u64, d_cap: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_commit_keccak_dev(
+        ctx: *mut P2hotCtx, d_cols: *const u64, col_stride: usize, W: usize, log_n: c_uint, rate_bits: c_uint, cap_height: c_uint,
+        is_values: c_int, row_begin: usize, row_count: usize, d_coeffs: *mut u64, coeff_stride: usize, d_lde: *mut u64, lde_stride: usize,
+        d_leaves: *mut u64, d_digests: *mut u64, d_cap: *mut u64, hash_size: c_uint,
     ) -> c_int;
     // ---- Challenger
     pub fn p2hot_challenger_create(ctx: *mut P2hotCtx, out: *mut *mut P2hotChallenger) -> c_int;
@@ -458,6 +473,19 @@ pub fn applies<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D
         && type_name::<C::Hasher>() == type_name::<PoseidonHash>()
         && core::mem::size_of::<F>() == 8
         && core::mem::size_of::<<C::Hasher as Hasher<F>>::Hash>() == 32
+}
+
+/// Does the GPU commitment apply to this instantiation with a Keccak tree?  KeccakGoldilocksConfig (plonk/config.rs:118-126,
+/// `Hasher = KeccakHash<25>`: the outer proof of a recursion chain) gets the LDE and the KeccakHash<25> tree of from_values /
+/// from_coeffs on the GPU (`commit_keccak`).  `applies` stays false for it, so FRI, the grind, the challenger and the quotient
+/// take the CPU bodies.
+pub fn applies_keccak_commit<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>() -> bool {
+    enabled()
+        && D == 2
+        && type_name::<F>() == type_name::<GoldilocksField>()
+        && type_name::<C::Hasher>() == type_name::<KeccakHash<25>>()
+        && core::mem::size_of::<F>() == 8
+        && core::mem::size_of::<<C::Hasher as Hasher<F>>::Hash>() == 25
 }
 
 #[inline]
@@ -743,6 +771,63 @@ pub(crate) fn commit_with_salts<F: RichField + Extendable<D>, C: GenericConfig<D
         degree_log: log_n,
         rate_bits,
         blinding: !salts.is_empty(),
+    }
+}
+
+/// `commit` for KeccakGoldilocksConfig (`applies_keccak_commit`): the library builds the KeccakHash<25> tree, whose digests come
+/// back in 32-byte slots (bytes 0..25, the rest zero) and are compacted into `BytesHash<25>` here.  The batch is an ordinary
+/// host-side one -- `leaves`, `digests` and `cap` filled, no `device` handle -- because the CPU `prove_openings` consumes it.
+pub fn commit_keccak<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>(
+    cols: &[&[F]],
+    rate_bits: usize,
+    cap_height: usize,
+    is_values: bool,
+    blinding: bool,
+) -> PolynomialBatch<F, C, D> {
+    let hash_n = core::mem::size_of::<<C::Hasher as Hasher<F>>::Hash>();
+    let w = cols.len();
+    let n = cols[0].len(); // polynomials[0].len(), oracle.rs:90
+    let log_n = log2_strict(n);
+    assert!(cols.iter().all(|c| c.len() == n));
+    let big_n = n << rate_bits;
+    let salts: Vec<Vec<F>> = if blinding { (0..SALT_SIZE).map(|_| F::rand_vec(big_n)).collect() } else { Vec::new() };
+    let lw = w + salts.len();
+    let num_digests = 2 * (big_n - (1usize << cap_height));
+    let ptrs: Vec<*const u64> = cols.iter().map(|c| words(c)).collect();
+    let salt_ptrs: Vec<*const u64> = salts.iter().map(|v| words(v)).collect();
+    let mut coeff_vecs: Vec<Out<F>> = (0..w).map(|_| Out::<F>::new(n, true)).collect();
+    let coeff_ptrs: Vec<*mut u64> = coeff_vecs.iter_mut().map(|o| o.ptr()).collect();
+    let mut flat = Out::<F>::new(big_n * lw, true); // row-major, committed order (MerkleTree::leaves)
+    let mut slots = Out::<[u64; 4]>::new(num_digests, true);
+    let mut cap_slots = Out::<[u64; 4]>::new(1 << cap_height, true);
+    with_ctx(|ctx| {
+        let rc = unsafe {
+            p2hot_commit_salted(
+                ctx, ptrs.as_ptr(), w, log_n as c_uint, rate_bits as c_uint, cap_height as c_uint, is_values as c_int,
+                P2HOT_COEFFS_PER_COLUMN | hash_keccak_flag(hash_n), salt_ptrs.as_ptr(), salt_ptrs.len(), coeff_ptrs.as_ptr() as *mut u64,
+                flat.ptr(), slots.ptr(), cap_slots.ptr(), core::ptr::null_mut(),
+            )
+        };
+        check(ctx, rc, "p2hot_commit_salted (KeccakHash)");
+    });
+    let (flat, slots, cap_slots) = unsafe { (flat.finish(), slots.finish(), cap_slots.finish()) };
+    let polynomials = coeff_vecs.into_iter().map(|o| PolynomialCoeffs::new(unsafe { o.finish() })).collect();
+    let compact = |s: &[u64; 4]| {
+        let mut b = [0u8; 32];
+        for (i, x) in s.iter().enumerate() {
+            b[8 * i..8 * i + 8].copy_from_slice(&x.to_le_bytes());
+        }
+        <C::Hasher as Hasher<F>>::Hash::from_bytes(&b[..hash_n])
+    };
+    let digests: Vec<_> = slots.par_iter().map(compact).collect();
+    let cap: Vec<_> = cap_slots.iter().map(compact).collect();
+    let leaves: Vec<Vec<F>> = flat.par_chunks_exact(lw).map(|r| r.to_vec()).collect();
+    PolynomialBatch {
+        polynomials,
+        merkle_tree: MerkleTree { leaves, digests, cap: MerkleCap(cap), device: None },
+        degree_log: log_n,
+        rate_bits,
+        blinding,
     }
 }
 
@@ -1510,5 +1595,33 @@ mod tests {
         let q = &proof.proof.opening_proof.query_round_proofs[0].initial_trees_proof.evals_proofs;
         assert_eq!(q[1].0.len(), config.num_wires + SALT_SIZE, "the opened wires leaf carries its salt");
         data.verify(proof)
+    }
+
+    /// KeccakGoldilocksConfig: from_values / from_coeffs build the KeccakHash<25> tree on the GPU (`commit_keccak`) and equal
+    /// the CPU bodies field by field; blinded (fresh salts each run), the GPU batch's tree is the reference tree over its leaves
+    #[test]
+    fn keccak_config_commit_matches_the_cpu_prover() {
+        use crate::plonk::config::KeccakGoldilocksConfig;
+        type KC = KeccakGoldilocksConfig;
+        type KH = <KC as GenericConfig<D>>::Hasher;
+        type KBatch = PolynomialBatch<F, KC, D>;
+        assert!(applies_keccak_commit::<F, KC, D>() && !applies::<F, KC, D>(false));
+        for (w, log_n, rate_bits, cap_height) in [(3usize, 5usize, 2usize, 0usize), (135, 6, 3, 2), (20, 7, 1, 8)] {
+            let values: Vec<PolynomialValues<F>> = (0..w).map(|_| PolynomialValues::new(F::rand_vec(1 << log_n))).collect();
+            let cpu = on_cpu(|| KBatch::from_values(values.clone(), rate_bits, false, cap_height, &mut TimingTree::default(), None));
+            let gpu = KBatch::from_values(values.clone(), rate_bits, false, cap_height, &mut TimingTree::default(), None);
+            assert!(gpu.merkle_tree.device.is_none());
+            assert_eq!(cpu.merkle_tree.digests, gpu.merkle_tree.digests, "KeccakHash<25> digests");
+            assert_eq!(cpu, gpu);
+            let coeffs: Vec<PolynomialCoeffs<F>> = values.into_iter().map(|v| v.ifft()).collect();
+            let cpu = on_cpu(|| KBatch::from_coeffs(coeffs.clone(), rate_bits, false, cap_height, &mut TimingTree::default(), None));
+            let gpu = KBatch::from_coeffs(coeffs, rate_bits, false, cap_height, &mut TimingTree::default(), None);
+            assert_eq!(cpu, gpu);
+        }
+        let values: Vec<PolynomialValues<F>> = (0..9).map(|_| PolynomialValues::new(F::rand_vec(1 << 6))).collect();
+        let gpu = KBatch::from_values(values, 2, true, 1, &mut TimingTree::default(), None);
+        let tree = MerkleTree::<F, KH>::new(gpu.merkle_tree.leaves.clone(), 1);
+        assert_eq!(gpu.merkle_tree.leaves[0].len(), 9 + SALT_SIZE);
+        assert_eq!((tree.digests, tree.cap), (gpu.merkle_tree.digests.clone(), gpu.merkle_tree.cap.clone()));
     }
 }

@@ -19,6 +19,10 @@ COEFFS_PER_COLUMN = 2
 LEAVES_ASYNC = 4
 LEAVES_NATURAL = 8
 
+
+def HASH_KECCAK(n):  # P2HOT_HASH_KECCAK(n): the commit's tree hasher is KeccakHash<n> (flag bits 8..15)
+    return n << 8
+
 vp = C.c_void_p
 sz = C.c_size_t
 u = C.c_uint
@@ -79,9 +83,12 @@ SIGNATURES = {
     "p2hot_reverse_index_bits_dev": (i, [vp, vp, vp, sz, sz, u]),
     "p2hot_poseidon_permute_dev": (i, [vp, vp, sz]),
     "p2hot_merkle_dev": (i, [vp, vp, i, sz, sz, u, u, sz, sz, vp, vp]),
+    "p2hot_keccak256_dev": (i, [vp, vp, sz, sz, u, vp]),
+    "p2hot_keccak_merkle_dev": (i, [vp, vp, i, sz, sz, u, u, sz, sz, vp, vp, u]),
     "p2hot_field_selftest_dev": (i, [vp, vp, vp, sz, vp]),
     "p2hot_gather_rows_dev": (i, [vp, vp, sz, sz, sz, vp, sz, vp]),
     "p2hot_commit_dev": (i, [vp, vp, sz, sz, u, u, u, i, sz, sz, vp, sz, vp, sz, vp, vp, vp]),
+    "p2hot_commit_keccak_dev": (i, [vp, vp, sz, sz, u, u, u, i, sz, sz, vp, sz, vp, sz, vp, vp, vp, u]),
     "p2hot_challenger_create": (i, [vp, C.POINTER(vp)]),
     "p2hot_challenger_destroy": (None, [vp]),
     "p2hot_challenger_load": (i, [vp, C.POINTER(ChallengerState)]),

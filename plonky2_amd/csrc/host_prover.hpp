@@ -113,8 +113,10 @@ static int commit_host(p2hot_ctx *ctx, const uint64_t *const *cols, size_t W, un
     P2_TRY(check_log(ctx, log_n + rate_bits, "commit"));
     if (W == 0) P2_FAIL(ctx, P2HOT_EINVAL, "commit: no polynomials (the reference panics on polynomials[0], fri/oracle.rs:90)");
     if (!cols) P2_FAIL(ctx, P2HOT_EINVAL, "commit: null column table");
-    if (flags & ~(unsigned)(P2HOT_KEEP_VALUES | P2HOT_COEFFS_PER_COLUMN | P2HOT_LEAVES_ASYNC | P2HOT_LEAVES_NATURAL))
+    if (flags & ~(unsigned)(P2HOT_KEEP_VALUES | P2HOT_COEFFS_PER_COLUMN | P2HOT_LEAVES_ASYNC | P2HOT_LEAVES_NATURAL | P2HOT_HASH_MASK))
         P2_FAIL(ctx, P2HOT_EINVAL, "commit: unknown flags %#x", flags);
+    const unsigned hash_n = (flags & P2HOT_HASH_MASK) >> 8;  // 0 = Poseidon, else KeccakHash<hash_n>
+    if (hash_n) P2_TRY(check_hash_size(ctx, hash_n, "commit"));
     if ((flags & P2HOT_LEAVES_ASYNC) && !(leaves_out && handle_out))
         P2_FAIL(ctx, P2HOT_EINVAL, "commit: P2HOT_LEAVES_ASYNC needs leaves_out and handle_out (the handle owns the copy in flight)");
     if ((flags & P2HOT_LEAVES_NATURAL) && !leaves_out) P2_FAIL(ctx, P2HOT_EINVAL, "commit: P2HOT_LEAVES_NATURAL without leaves_out");
@@ -176,10 +178,11 @@ static int commit_host(p2hot_ctx *ctx, const uint64_t *const *cols, size_t W, un
     // leaving on the leaf stream -- as early as in the leaves-first order; the leaf sponge absorbs each block's columns on the
     // context's stream BESIDE them (the chunked order: the hashing, three quarters of the call, hides the uploads), so the call
     // returns as early as a call without leaves.  Neither single-stream order gives both (profiles/r05_async_ab.txt).
-    const bool xsplit = async_leaves && ctx->host_chunked_hash && ctx->host_async_split && nb > 1 && LW > 8 && LW <= 0xFFFFFFFFull;
+    // (a Keccak tree hashes after the last column instead: profiles/keccak_commit.json has what the chunked Poseidon order saves)
+    const bool xsplit = !hash_n && async_leaves && ctx->host_chunked_hash && ctx->host_async_split && nb > 1 && LW > 8 && LW <= 0xFFFFFFFFull;
     const bool leaves_first = ctx->host_leaves_first && leaves_out && LW && (nb > 1 || big_leaves) && !xsplit;
     const bool early_transpose = async_leaves && LW;  // the asynchronous copy: the matrix is transposed as soon as the last column is extended
-    const bool chunked = ctx->host_chunked_hash && nb > 1 && LW > 8 && LW <= 0xFFFFFFFFull && !leaves_first;
+    const bool chunked = !hash_n && ctx->host_chunked_hash && nb > 1 && LW > 8 && LW <= 0xFFFFFFFFull && !leaves_first;
     PoolBuf d_state(ctx);
     ForestGeom geom{};
     unsigned hashed = 0;  // columns the sponge has absorbed (a multiple of 8 until the end)
@@ -329,7 +332,7 @@ static int commit_host(p2hot_ctx *ctx, const uint64_t *const *cols, size_t W, un
             P2_TRY(absorb_upto(LW, true));  // what is left (the salts' chunks)
             P2_TRY(merkle_levels(ctx, geom, N));
         } else {
-            P2_TRY(p2hot_merkle_dev(ctx, d_lde.u(), 0, N, LW, log_N, cap_height, 0, N, d_dig.u(), d_cap.u()));
+            P2_TRY(merkle_dev_impl(ctx, d_lde.u(), 0, N, LW, log_N, cap_height, 0, N, d_dig.u(), d_cap.u(), hash_n));
         }
         if (leaves_out && LW && !leaves_first && !early_transpose) P2_TRY(transpose_rows(ctx, d_lde.u(), N, LW, N, d_leaves.u(), leaf_rev));
         // coefficient blocks go back while the leaf sponge runs: queued behind the uploads on the copy stream, each
@@ -391,7 +394,10 @@ static int commit_host(p2hot_ctx *ctx, const uint64_t *const *cols, size_t W, un
     if (leaves_ev) (void)hipEventDestroy(leaves_ev);
     rc = sync_checked(ctx, rc, "commit");
     if (rc == P2HOT_OK && e1 != hipSuccess) P2_FAIL(ctx, P2HOT_EHIP, "commit: %s", hipGetErrorString(e1));
-    if (rc == P2HOT_OK && handle_out) *handle_out = make_batch(ctx, d_lde, d_dig, d_work, keep_vals ? &d_vals : nullptr, W, log_n, rate_bits, cap_height, S);
+    if (rc == P2HOT_OK && handle_out) {
+        *handle_out = make_batch(ctx, d_lde, d_dig, d_work, keep_vals ? &d_vals : nullptr, W, log_n, rate_bits, cap_height, S);
+        (*handle_out)->hash_n = hash_n;
+    }
     if (leafcopy) {
         if (rc == P2HOT_OK && handle_out && *handle_out) {
             leafcopy->d_staging = d_leaves.p;  // stays alive behind the handle until the last block has landed
@@ -473,7 +479,10 @@ extern "C" int p2hot_commit_cols(p2hot_ctx *ctx, p2hot_cols *cols, unsigned rate
     const unsigned log_n = cols->log_n;
     P2_TRY(check_log(ctx, log_n + rate_bits, "commit_cols"));
     if (W == 0) P2_FAIL(ctx, P2HOT_EINVAL, "commit_cols: no polynomials (the reference panics on polynomials[0], fri/oracle.rs:90)");
-    if (flags & ~(unsigned)(P2HOT_KEEP_VALUES | P2HOT_COEFFS_PER_COLUMN)) P2_FAIL(ctx, P2HOT_EINVAL, "commit_cols: unknown flags %#x", flags);
+    if (flags & ~(unsigned)(P2HOT_KEEP_VALUES | P2HOT_COEFFS_PER_COLUMN | P2HOT_HASH_MASK))
+        P2_FAIL(ctx, P2HOT_EINVAL, "commit_cols: unknown flags %#x", flags);
+    const unsigned hash_n = (flags & P2HOT_HASH_MASK) >> 8;
+    if (hash_n) P2_TRY(check_hash_size(ctx, hash_n, "commit_cols"));
     uint64_t *const *coeffs_cols = (flags & P2HOT_COEFFS_PER_COLUMN) ? reinterpret_cast<uint64_t *const *>(coeffs_out) : nullptr;
     if (coeffs_cols)
         for (size_t c = 0; c < W; ++c)
@@ -508,8 +517,8 @@ extern "C" int p2hot_commit_cols(p2hot_ctx *ctx, p2hot_cols *cols, unsigned rate
             P2HOT_LAUNCH(ntt::canon_kernel, dim3(cdiv(W * n, 256)), dim3(256), 0, ctx->stream, co, W * n);
             P2_LAUNCH_CHECK(ctx);
         }
-        P2_TRY(p2hot_commit_dev(ctx, co, n, W, log_n, rate_bits, cap_height, 0, 0, N, nullptr, 0, d_lde.u(), N,
-                                leaves_out ? d_leaves.u() : nullptr, d_dig.u(), d_cap.u()));
+        P2_TRY(commit_dev_impl(ctx, co, n, W, log_n, rate_bits, cap_height, 0, 0, N, nullptr, 0, d_lde.u(), N,
+                               leaves_out ? d_leaves.u() : nullptr, d_dig.u(), d_cap.u(), hash_n));
         if (coeffs_cols) {
             for (size_t c = 0; c < W; ++c) P2_HIP(ctx, hipMemcpyAsync(coeffs_cols[c], co + c * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         } else if (coeffs_out && W) {
@@ -526,6 +535,7 @@ extern "C" int p2hot_commit_cols(p2hot_ctx *ctx, p2hot_cols *cols, unsigned rate
             *handle_out = make_batch(ctx, d_lde, d_dig, d_coef, &d_in, W, log_n, rate_bits, cap_height);
         else
             *handle_out = make_batch(ctx, d_lde, d_dig, d_in, nullptr, W, log_n, rate_bits, cap_height);
+        (*handle_out)->hash_n = hash_n;
     }
     return rc;
 }
@@ -949,6 +959,9 @@ extern "C" int p2hot_prove_openings(p2hot_ctx *ctx, const p2hot_fri_batch_info *
     std::vector<OracleView> views;
     for (size_t o = 0; o < n_oracles; ++o) {
         if (!oracles[o] || oracles[o]->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: oracle %zu is null or belongs to another context", o);
+        if (oracles[o]->hash_n)
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings: oracle %zu is a KeccakHash<%u> tree (FRI for the Keccak config runs on the CPU)", o,
+                    oracles[o]->hash_n);
         if (oracles[o]->log_n != oracles[0]->log_n || (fp && (oracles[o]->rate_bits != fp->rate_bits || oracles[o]->cap_height != fp->cap_height)))
             P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: oracle %zu was committed with another degree / rate / cap height", o);
         views.push_back(OracleView{oracles[o]->d_coef, oracles[o]->d_lde, oracles[o]->d_dig, oracles[o]->W, oracles[o]->N, oracles[o]->S,
@@ -1012,6 +1025,9 @@ extern "C" int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_f
         for (size_t o = 0; o < n_oracles; ++o) {
             const p2hot_batch *B = oracles[j * n_oracles + o];
             if (!B || B->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings_many: oracle %zu of proof %zu is null or belongs to another context", o, j);
+            if (B->hash_n)
+                P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings_many: oracle %zu of proof %zu is a KeccakHash<%u> tree (FRI for the Keccak config runs on the CPU)",
+                        o, j, B->hash_n);
             if (B->log_n != oracles[0]->log_n || (fp && (B->rate_bits != fp->rate_bits || B->cap_height != fp->cap_height)))
                 P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings_many: oracle %zu of proof %zu was committed with another degree / rate / cap height", o, j);
             views[j].push_back(OracleView{B->d_coef, B->d_lde, B->d_dig, B->W, B->N, B->S, B->lde_stride, B->coef_stride});

@@ -11,11 +11,13 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "fri.hpp"
 #include "plonk.hpp"
 #include "merkle.hpp"
+#include "keccak.hpp"
 #include "ntt.hpp"
 #include "nttl.hpp"
 
@@ -1199,12 +1201,20 @@ static int forest_geom(p2hot_ctx *ctx, unsigned log_leaves, unsigned cap_height,
 }
 
 // leaf sponge for the forest leaves [leaf_offset, leaf_offset + count) on `stream`
+// hash_n: 0 = PoseidonHash, 1..32 = KeccakHash<hash_n> (keccak.hpp)
 template <class Reader>
 static int hash_leaves_range(p2hot_ctx *ctx, hipStream_t stream, Reader rd, size_t W, const ForestGeom &g,
-                             size_t leaf_offset, size_t count) {
+                             size_t leaf_offset, size_t count, unsigned hash_n = 0) {
     if (count == 0) return P2HOT_OK;
     ProfScope ps(ctx, "hash_leaves", stream, true);
-    if (count <= ctx->row_threshold) {  // a few thousand leaves at most: 16 lanes per leaf, the lowest latency per permutation
+    if (hash_n) {
+        if constexpr (std::is_same<Reader, merkle::FriPlanarReader>::value) {  // FRI trees stay Poseidon (no Keccak FRI)
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "hash_leaves: Keccak FRI trees");
+        } else {
+            P2HOT_LAUNCH((keccak::keccak_leaves_kernel<Reader>), dim3(cdiv(count, 256)), dim3(256), 0, stream, rd, (unsigned)W,
+                         leaf_offset, count, g.h, hash_n, g.dig, g.cap);
+        }
+    } else if (count <= ctx->row_threshold) {  // a few thousand leaves at most: 16 lanes per leaf, the lowest latency per permutation
         P2HOT_LAUNCH((merkle::hash_leaves_row_kernel<Reader>), dim3(cdiv(16 * count, 256)), dim3(256), 0, stream, rd, (unsigned)W,
                      leaf_offset, count, g.h, g.dig, g.cap);
     } else if (count <= ctx->quad_threshold) {  // too few permutations to fill the chip: 4 lanes per leaf, ~3x lower latency
@@ -1231,8 +1241,17 @@ static int hash_leaves_chunks(p2hot_ctx *ctx, hipStream_t stream, Reader rd, siz
     return P2HOT_OK;
 }
 
-static int merkle_levels(p2hot_ctx *ctx, const ForestGeom &g, size_t leaf_count) {
+static int merkle_levels(p2hot_ctx *ctx, const ForestGeom &g, size_t leaf_count, unsigned hash_n = 0) {
     ProfScope ps(ctx, "merkle_levels");
+    if (hash_n) {
+        for (unsigned level = 1; level <= g.h; ++level) {
+            const size_t nodes = leaf_count >> level;
+            P2HOT_LAUNCH(keccak::keccak_level_kernel, dim3(cdiv(nodes, 256)), dim3(256), 0, ctx->stream, g.dig, g.cap, g.h, level,
+                         nodes, hash_n);
+            P2_LAUNCH_CHECK(ctx);
+        }
+        return P2HOT_OK;
+    }
     // One launch per level.  Walking the top levels of every cap subtree in one launch (a 1024-thread workgroup per subtree,
     // a barrier per level, word-per-lane permutations) was built and measured at recursion size: 146 us per tree against
     // 7 x 12.4 -- a level's nodes then share one CU (four waves per SIMD) instead of spreading over the chip
@@ -1254,39 +1273,102 @@ static int merkle_levels(p2hot_ctx *ctx, const ForestGeom &g, size_t leaf_count)
 
 template <class Reader>
 static int merkle_forest(p2hot_ctx *ctx, Reader rd, size_t W, unsigned log_leaves, unsigned cap_height,
-                         size_t leaf_begin, size_t leaf_count, u64 *d_digests, u64 *d_cap) {
+                         size_t leaf_begin, size_t leaf_count, u64 *d_digests, u64 *d_cap, unsigned hash_n = 0) {
     ForestGeom g;
     P2_TRY(forest_geom(ctx, log_leaves, cap_height, leaf_begin, leaf_count, d_digests, d_cap, &g));
     if (leaf_count == 0) return P2HOT_OK;
-    P2_TRY(hash_leaves_range(ctx, ctx->stream, rd, W, g, 0, leaf_count));
-    return merkle_levels(ctx, g, leaf_count);
+    P2_TRY(hash_leaves_range(ctx, ctx->stream, rd, W, g, 0, leaf_count, hash_n));
+    return merkle_levels(ctx, g, leaf_count, hash_n);
 }
+
+// KeccakHash<N> digests are N = 1..32 bytes (the reference slices hash_bytes[..N] of a 32-byte output, keccak.rs:110-112)
+static int check_hash_size(p2hot_ctx *ctx, unsigned hash_size, const char *what) {
+    if (hash_size == 0 || hash_size > 32) P2_FAIL(ctx, P2HOT_EINVAL, "%s: Keccak hash size %u (1..32 bytes)", what, hash_size);
+    return P2HOT_OK;
+}
+
+static int merkle_dev_impl(p2hot_ctx *ctx, const uint64_t *d_leaves, int layout, size_t leaf_stride, size_t W, unsigned log_leaves,
+                           unsigned cap_height, size_t leaf_begin, size_t leaf_count, uint64_t *d_digests, uint64_t *d_cap,
+                           unsigned hash_n);
 
 extern "C" int p2hot_merkle_dev(p2hot_ctx *ctx, const uint64_t *d_leaves, int layout, size_t leaf_stride, size_t W,
                                 unsigned log_leaves, unsigned cap_height, size_t leaf_begin, size_t leaf_count,
                                 uint64_t *d_digests, uint64_t *d_cap) {
     if (!ctx) return P2HOT_EINVAL;
     DeviceGuard dev_guard_(ctx);
+    return merkle_dev_impl(ctx, d_leaves, layout, leaf_stride, W, log_leaves, cap_height, leaf_begin, leaf_count, d_digests, d_cap, 0);
+}
+
+extern "C" int p2hot_keccak_merkle_dev(p2hot_ctx *ctx, const uint64_t *d_leaves, int layout, size_t leaf_stride, size_t W,
+                                       unsigned log_leaves, unsigned cap_height, size_t leaf_begin, size_t leaf_count,
+                                       uint64_t *d_digests, uint64_t *d_cap, unsigned hash_size) {
+    if (!ctx) return P2HOT_EINVAL;
+    DeviceGuard dev_guard_(ctx);
+    P2_TRY(check_hash_size(ctx, hash_size, "keccak_merkle"));
+    return merkle_dev_impl(ctx, d_leaves, layout, leaf_stride, W, log_leaves, cap_height, leaf_begin, leaf_count, d_digests, d_cap,
+                           hash_size);
+}
+
+extern "C" int p2hot_keccak256_dev(p2hot_ctx *ctx, const uint8_t *d_msgs, size_t msg_bytes, size_t count, unsigned domain_byte,
+                                   uint64_t *d_out) {
+    if (!ctx) return P2HOT_EINVAL;
+    DeviceGuard dev_guard_(ctx);
+    if (count == 0) return P2HOT_OK;
+    if ((msg_bytes && !d_msgs) || !d_out) P2_FAIL(ctx, P2HOT_EINVAL, "keccak256: null pointer");
+    if (domain_byte > 0xFF) P2_FAIL(ctx, P2HOT_EINVAL, "keccak256: domain byte %#x is not a byte", domain_byte);
+    P2HOT_LAUNCH(keccak::keccak_bytes_kernel, dim3(cdiv(count, 256)), dim3(256), 0, ctx->stream, d_msgs, msg_bytes, count,
+                 (u64)domain_byte, d_out);
+    P2_LAUNCH_CHECK(ctx);
+    return P2HOT_OK;
+}
+
+static int merkle_dev_impl(p2hot_ctx *ctx, const uint64_t *d_leaves, int layout, size_t leaf_stride, size_t W, unsigned log_leaves,
+                           unsigned cap_height, size_t leaf_begin, size_t leaf_count, uint64_t *d_digests, uint64_t *d_cap,
+                           unsigned hash_n) {
     if (W > 0 && !d_leaves) P2_FAIL(ctx, P2HOT_EINVAL, "merkle: null leaves");
     if (W > 0xFFFFFFFFull) P2_FAIL(ctx, P2HOT_EINVAL, "merkle: leaf too wide");
     if (layout == 0) {
         if (W > 0 && leaf_stride < leaf_count) P2_FAIL(ctx, P2HOT_EINVAL, "merkle: leaf_stride < leaf_count");
         return merkle_forest(ctx, merkle::ColMajorReader{d_leaves, leaf_stride}, W, log_leaves, cap_height, leaf_begin,
-                             leaf_count, d_digests, d_cap);
+                             leaf_count, d_digests, d_cap, hash_n);
     } else if (layout == 1) {
         return merkle_forest(ctx, merkle::RowMajorReader{d_leaves, W}, W, log_leaves, cap_height, leaf_begin, leaf_count,
-                             d_digests, d_cap);
+                             d_digests, d_cap, hash_n);
     }
     P2_FAIL(ctx, P2HOT_EINVAL, "merkle: unknown layout %d", layout);
 }
 
 // ------------------------------------------------------------------ PolynomialBatch
+static int commit_dev_impl(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_stride, size_t W, unsigned log_n, unsigned rate_bits,
+                           unsigned cap_height, int is_values, size_t row_begin, size_t row_count, uint64_t *d_coeffs,
+                           size_t coeff_stride, uint64_t *d_lde, size_t lde_stride, uint64_t *d_leaves, uint64_t *d_digests,
+                           uint64_t *d_cap, unsigned hash_n);
+
 extern "C" int p2hot_commit_dev(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_stride, size_t W, unsigned log_n,
                                 unsigned rate_bits, unsigned cap_height, int is_values, size_t row_begin,
                                 size_t row_count, uint64_t *d_coeffs, size_t coeff_stride, uint64_t *d_lde,
                                 size_t lde_stride, uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap) {
     if (!ctx) return P2HOT_EINVAL;
     DeviceGuard dev_guard_(ctx);
+    return commit_dev_impl(ctx, d_cols, col_stride, W, log_n, rate_bits, cap_height, is_values, row_begin, row_count, d_coeffs,
+                           coeff_stride, d_lde, lde_stride, d_leaves, d_digests, d_cap, 0);
+}
+
+extern "C" int p2hot_commit_keccak_dev(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_stride, size_t W, unsigned log_n,
+                                       unsigned rate_bits, unsigned cap_height, int is_values, size_t row_begin, size_t row_count,
+                                       uint64_t *d_coeffs, size_t coeff_stride, uint64_t *d_lde, size_t lde_stride,
+                                       uint64_t *d_leaves, uint64_t *d_digests, uint64_t *d_cap, unsigned hash_size) {
+    if (!ctx) return P2HOT_EINVAL;
+    DeviceGuard dev_guard_(ctx);
+    P2_TRY(check_hash_size(ctx, hash_size, "commit_keccak"));
+    return commit_dev_impl(ctx, d_cols, col_stride, W, log_n, rate_bits, cap_height, is_values, row_begin, row_count, d_coeffs,
+                           coeff_stride, d_lde, lde_stride, d_leaves, d_digests, d_cap, hash_size);
+}
+
+static int commit_dev_impl(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_stride, size_t W, unsigned log_n, unsigned rate_bits,
+                           unsigned cap_height, int is_values, size_t row_begin, size_t row_count, uint64_t *d_coeffs,
+                           size_t coeff_stride, uint64_t *d_lde, size_t lde_stride, uint64_t *d_leaves, uint64_t *d_digests,
+                           uint64_t *d_cap, unsigned hash_n) {
     P2_TRY(check_log(ctx, log_n + rate_bits, "commit"));
     const size_t n = (size_t)1 << log_n;
     const unsigned log_N = log_n + rate_bits;
@@ -1342,17 +1424,17 @@ extern "C" int p2hot_commit_dev(p2hot_ctx *ctx, const uint64_t *d_cols, size_t c
                                        row_begin + b * n, n, d_lde + b * n, lde_stride));
             P2_HIP(ctx, hipEventRecord(ctx->fork_events[b], ctx->stream));
             P2_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->fork_events[b], 0));
-            P2_TRY(hash_leaves_range(ctx, ctx->side, merkle::ColMajorReader{d_lde, lde_stride}, W, g, b * n, n));
+            P2_TRY(hash_leaves_range(ctx, ctx->side, merkle::ColMajorReader{d_lde, lde_stride}, W, g, b * n, n, hash_n));
         }
         P2_HIP(ctx, hipEventRecord(ctx->join_event, ctx->side));
         P2_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->join_event, 0));
-        P2_TRY(merkle_levels(ctx, g, row_count));
+        P2_TRY(merkle_levels(ctx, g, row_count, hash_n));
     } else
     {
         (void)blocks;
         P2_TRY(coset_lde_impl(ctx, coeff_src, W, coeff_src_stride, log_n, rate_bits, gl::COSET_SHIFT, row_begin, row_count, d_lde,
                               lde_stride, brin.src ? &brin : nullptr));
-        P2_TRY(p2hot_merkle_dev(ctx, d_lde, 0, lde_stride, W, log_N, cap_height, row_begin, row_count, d_digests, d_cap));
+        P2_TRY(merkle_dev_impl(ctx, d_lde, 0, lde_stride, W, log_N, cap_height, row_begin, row_count, d_digests, d_cap, hash_n));
     }
     if (d_leaves) P2_TRY(p2hot_transpose_dev(ctx, d_lde, lde_stride, W, row_count, d_leaves));
     return P2HOT_OK;
@@ -1917,6 +1999,7 @@ struct p2hot_batch {
     unsigned log_n = 0, rate_bits = 0;
     bool owned = true;      // false: a view over caller-owned device buffers (p2hot_batch_wrap_dev)
     size_t S = 0;           // blinding (oracle.rs:123-137): salt columns W .. W+S-1 of d_lde; a leaf is W + S words wide
+    unsigned hash_n = 0;    // the tree's hasher: 0 = PoseidonHash, 1..32 = KeccakHash<hash_n> (digests in 32-byte slots)
     // a member of a batched commitment (p2hot_commit_many): its columns are interleaved with the other proofs' ([W][M][N]), the
     // blocks are shared and go back to the pool with the last member
     size_t lde_stride = 0, coef_stride = 0;  // elements between consecutive columns; 0 = N / n

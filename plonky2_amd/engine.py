@@ -173,8 +173,10 @@ class Engine:
         self.check(self.lib.p2hot_poseidon_permute_dev(self.ctx, self.ptr(states), count))
         return states
 
-    def merkle(self, leaves, layout, W, log_leaves, cap_height, leaf_begin=0, leaf_count=None, digests=None, cap=None):
-        """layout 0: leaves [W][leaf_count] column-major; layout 1: [leaf_count][W] row-major"""
+    def merkle(self, leaves, layout, W, log_leaves, cap_height, leaf_begin=0, leaf_count=None, digests=None, cap=None,
+               hash_size=0):
+        """layout 0: leaves [W][leaf_count] column-major; layout 1: [leaf_count][W] row-major.
+        hash_size 0: PoseidonHash; 1..32: KeccakHash<hash_size> (p2hot_keccak_merkle_dev)"""
         n_leaves = 1 << log_leaves
         if leaf_count is None:
             leaf_count = n_leaves - leaf_begin
@@ -184,9 +186,27 @@ class Engine:
         if cap is None:
             cap = self.mem.zeros(1 << cap_height, 4)
         stride = leaves.shape[1] if (layout == 0 and W) else 0
-        self.check(self.lib.p2hot_merkle_dev(self.ctx, self.ptr(leaves) if W else None, layout, stride, W, log_leaves,
-                                             cap_height, leaf_begin, leaf_count, self.ptr(digests), self.ptr(cap)))
+        args = (self.ctx, self.ptr(leaves) if W else None, layout, stride, W, log_leaves, cap_height, leaf_begin, leaf_count,
+                self.ptr(digests), self.ptr(cap))
+        if hash_size:
+            self.check(self.lib.p2hot_keccak_merkle_dev(*args, hash_size))
+        else:
+            self.check(self.lib.p2hot_merkle_dev(*args))
         return digests[:nd], cap
+
+    def keccak256(self, msgs, domain=0x01):
+        """p2hot_keccak256_dev.  msgs: host uint8 [count][msg_bytes].  Returns host uint8 [count][32]."""
+        msgs = np.ascontiguousarray(np.asarray(msgs, dtype=np.uint8))
+        count, msg_bytes = msgs.shape
+        if count == 0:
+            return np.zeros((0, 32), dtype=np.uint8)
+        # the device copy travels as words (the engine's buffers are uint64): pad the byte string to a whole word
+        flat = np.zeros(((count * msg_bytes + 7) // 8) * 8 or 8, dtype=np.uint8)
+        flat[:count * msg_bytes] = msgs.reshape(-1)
+        d_msgs = self.dev(flat.view(np.uint64))
+        out = self.mem.zeros(count, 4)
+        self.check(self.lib.p2hot_keccak256_dev(self.ctx, self.ptr(d_msgs), msg_bytes, count, domain, self.ptr(out)))
+        return np.ascontiguousarray(self.host(out)).view(np.uint8).reshape(count, 32)
 
     def gather_rows(self, colmajor, idx):
         W, stride = colmajor.shape
@@ -202,8 +222,9 @@ class Engine:
         return out
 
     def commit(self, cols, log_n, rate_bits, cap_height, is_values, row_begin=0, row_count=None, want_leaves=False,
-               digests=None, cap=None):
-        """p2hot_commit_dev.  cols: device [W][n].  Returns dict of device buffers."""
+               digests=None, cap=None, hash_size=0):
+        """p2hot_commit_dev (hash_size 0) or p2hot_commit_keccak_dev (KeccakHash<hash_size>).  cols: device [W][n].
+        Returns dict of device buffers."""
         W, stride = cols.shape
         n = 1 << log_n
         log_N = log_n + rate_bits
@@ -218,10 +239,13 @@ class Engine:
             digests = self.mem.zeros(max(nd, 1), 4)
         if cap is None:
             cap = self.mem.zeros(1 << cap_height, 4)
-        self.check(self.lib.p2hot_commit_dev(
-            self.ctx, self.ptr(cols), stride, W, log_n, rate_bits, cap_height, 1 if is_values else 0, row_begin,
-            row_count, self.ptr(coeffs), coeffs.shape[1] if W else n, self.ptr(lde), row_count, self.ptr(leaves),
-            self.ptr(digests), self.ptr(cap)))
+        args = (self.ctx, self.ptr(cols), stride, W, log_n, rate_bits, cap_height, 1 if is_values else 0, row_begin,
+                row_count, self.ptr(coeffs), coeffs.shape[1] if W else n, self.ptr(lde), row_count, self.ptr(leaves),
+                self.ptr(digests), self.ptr(cap))
+        if hash_size:
+            self.check(self.lib.p2hot_commit_keccak_dev(*args, hash_size))
+        else:
+            self.check(self.lib.p2hot_commit_dev(*args))
         return {"coeffs": coeffs, "lde": lde, "leaves": leaves, "digests": digests[:nd], "cap": cap}
 
 

@@ -17,6 +17,7 @@ import numpy as np
 
 from .. import _lib
 from ..engine import default_engine
+from ..hash.keccak import hash_size
 from ..hash.merkle_tree import MerkleTree
 
 P = 0xFFFFFFFF00000001
@@ -77,6 +78,7 @@ class PolynomialBatch:
         self.rate_bits = rate_bits
         self.cap_height = cap_height
         self.blinding = blinding
+        self.hasher = None  # PoseidonHash, or the KeccakHash the batch was committed with (_build)
         N = 1 << (degree_log + rate_bits)
         own = self._owner
         self.merkle_tree = MerkleTree(None, digests, cap, cap_height, n_leaves=N,
@@ -98,28 +100,41 @@ class PolynomialBatch:
 
     @classmethod
     def from_values(cls, values, rate_bits, blinding, cap_height, timing=None, fft_root_table=None, engine=None,
-                    keep_values=False, salts=None):
+                    keep_values=False, salts=None, hasher=None):
         """oracle.rs:57-79.  values: [W][n] (host ndarray or device buffer), values on H_n.
         keep_values: keep the values on the device for plonk.prover (P2HOT_KEEP_VALUES).
         blinding=True: `salts` = the SALT_SIZE random vectors [4][N] the reference draws with F::rand_vec (oracle.rs:133-137);
-        the caller owns the randomness."""
-        return cls._build(values, rate_bits, blinding, cap_height, True, engine, keep_values, salts)
+        the caller owns the randomness.
+        hasher: None = PoseidonHash; hash.keccak.KeccakHash(N) builds the tree with KeccakHash<N> (host columns only: the
+        batch records its hasher, and prove_openings refuses it)."""
+        return cls._build(values, rate_bits, blinding, cap_height, True, engine, keep_values, salts, hasher)
 
     @classmethod
-    def from_coeffs(cls, polynomials, rate_bits, blinding, cap_height, timing=None, fft_root_table=None, engine=None, salts=None):
+    def from_coeffs(cls, polynomials, rate_bits, blinding, cap_height, timing=None, fft_root_table=None, engine=None, salts=None,
+                    hasher=None):
         """oracle.rs:82-112.  polynomials: [W][n] coefficients."""
-        return cls._build(polynomials, rate_bits, blinding, cap_height, False, engine, False, salts)
+        return cls._build(polynomials, rate_bits, blinding, cap_height, False, engine, False, salts, hasher)
 
     @classmethod
-    def _build(cls, cols, rate_bits, blinding, cap_height, is_values, engine, keep_values, salts=None):
+    def _build(cls, cols, rate_bits, blinding, cap_height, is_values, engine, keep_values, salts=None, hasher=None):
         eng = engine or default_engine()
+        hflag = _lib.HASH_KECCAK(hash_size(hasher))
+        if hflag and eng.mem.is_buffer(cols):
+            raise ValueError("a KeccakHash batch is committed from host columns or DeviceColumns "
+                             "(device buffers: Engine.commit(..., hash_size=N))")
+        batch = cls._build_any(cols, rate_bits, blinding, cap_height, is_values, eng, keep_values, salts, hflag)
+        batch.hasher = batch.merkle_tree.hasher = hasher
+        return batch
+
+    @classmethod
+    def _build_any(cls, cols, rate_bits, blinding, cap_height, is_values, eng, keep_values, salts, hflag):
         if blinding:
             if salts is None:
                 raise ValueError("blinding=True needs the caller's salt vectors (the reference draws them from OsRng, "
                                  "oracle.rs:133-137): pass salts=[SALT_SIZE][N]")
-            return cls._build_salted(cols, rate_bits, cap_height, is_values, eng, keep_values, salts)
+            return cls._build_salted(cols, rate_bits, cap_height, is_values, eng, keep_values, salts, hflag)
         if isinstance(cols, DeviceColumns):
-            return cls._from_device_columns(cols, rate_bits, cap_height, is_values, eng, keep_values)
+            return cls._from_device_columns(cols, rate_bits, cap_height, is_values, eng, keep_values, hflag)
         if not eng.mem.is_buffer(cols):
             cols = np.asarray(cols, dtype=np.uint64)
         if cols.ndim != 2:
@@ -141,12 +156,12 @@ class PolynomialBatch:
         ptrs = (C.c_void_p * max(W, 1))(*[cols[c].ctypes.data for c in range(W)])
         cap = np.zeros((1 << cap_height, 4), dtype=np.uint64)
         eng.check(eng.lib.p2hot_commit(eng.ctx, ptrs, W, log_n, rate_bits, cap_height, 1 if is_values else 0,
-                                       _lib.KEEP_VALUES if (keep_values and is_values) else 0, None, None, None,
+                                       (_lib.KEEP_VALUES if (keep_values and is_values) else 0) | hflag, None, None, None,
                                        cap.ctypes.data, C.byref(h)))
         return cls(eng, h, W, log_n, rate_bits, cap_height, cap)
 
     @classmethod
-    def _build_salted(cls, cols, rate_bits, cap_height, is_values, eng, keep_values, salts):
+    def _build_salted(cls, cols, rate_bits, cap_height, is_values, eng, keep_values, salts, hflag=0):
         """p2hot_commit_salted: host columns + host salt vectors (what the Rust shim passes for a zk config)"""
         cols = np.ascontiguousarray(np.asarray(cols, dtype=np.uint64))
         salts = np.ascontiguousarray(np.asarray(salts, dtype=np.uint64))
@@ -164,18 +179,19 @@ class PolynomialBatch:
         cap = np.zeros((1 << cap_height, 4), dtype=np.uint64)
         h = C.c_void_p()
         eng.check(eng.lib.p2hot_commit_salted(eng.ctx, ptrs, W, log_n, rate_bits, cap_height, 1 if is_values else 0,
-                                              _lib.KEEP_VALUES if (keep_values and is_values) else 0, sptrs, S, None, None, None,
+                                              (_lib.KEEP_VALUES if (keep_values and is_values) else 0) | hflag, sptrs, S, None,
+                                              None, None,
                                               cap.ctypes.data, C.byref(h)))
         return cls(eng, h, W, log_n, rate_bits, cap_height, cap, blinding=True, salt=S)
 
     @classmethod
-    def _from_device_columns(cls, dc, rate_bits, cap_height, is_values, eng, keep_values):
+    def _from_device_columns(cls, dc, rate_bits, cap_height, is_values, eng, keep_values, hflag=0):
         W, log_n = dc.width, dc.degree_log
         cap = np.zeros((1 << cap_height, 4), dtype=np.uint64)
         h = C.c_void_p()
         handle, dc._h = dc._h, None  # consumed by the library ...
         rc = eng.lib.p2hot_commit_cols(eng.ctx, handle, rate_bits, cap_height, 1 if is_values else 0,
-                                       _lib.KEEP_VALUES if (keep_values and is_values) else 0, None, None, None,
+                                       (_lib.KEEP_VALUES if (keep_values and is_values) else 0) | hflag, None, None, None,
                                        cap.ctypes.data, C.byref(h))
         if rc in (_lib.EBUSY, _lib.EINVAL):
             dc._h = handle  # ... except when the call never touched it (include/p2hot.h: both codes mean "not consumed")

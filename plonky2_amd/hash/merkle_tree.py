@@ -16,6 +16,11 @@ class MerkleCap:  # merkle_tree.rs:19
     def flatten(self):
         return self.entries.reshape(-1)
 
+    def to_bytes(self, n):
+        """the entries as BytesHash<n> (KeccakHash<n> trees: bytes 0..n of each 32-byte slot), a list of bytes"""
+        from .keccak import to_bytes
+        return [bytes(d) for d in to_bytes(self.entries, n)]
+
 
 class MerkleTree:
     """leaves [n][w]; digests [2*(n - 2^cap_height)][4] in the reference layout (:50-57); cap [2^cap_height][4].
@@ -38,6 +43,7 @@ class MerkleTree:
         self.cap = MerkleCap(cap)
         self.cap_height = cap_height
         self.n_leaves = n_leaves if n_leaves is not None else len(leaves)
+        self.hasher = None  # PoseidonHash; MerkleTree.new / PolynomialBatch set a KeccakHash here
 
     @property
     def digests(self):
@@ -46,7 +52,10 @@ class MerkleTree:
         return self._digests
 
     @classmethod
-    def new(cls, leaves, cap_height, engine=None):  # merkle_tree.rs:193-224
+    def new(cls, leaves, cap_height, engine=None, hasher=None):  # merkle_tree.rs:193-224
+        """hasher: None = PoseidonHash, or a hash.keccak.KeccakHash(N) (digests in 32-byte slots, MerkleCap.to_bytes(N))"""
+        from .keccak import hash_size
+        hs = hash_size(hasher)
         eng = engine or default_engine()
         leaves_h = np.ascontiguousarray(np.asarray(leaves, dtype=np.uint64))
         if leaves_h.ndim != 2:
@@ -56,8 +65,10 @@ class MerkleTree:
         if n != 1 << log_n:
             raise ValueError("number of leaves must be a power of two")  # log2_strict, :194
         d_leaves = eng.dev(leaves_h)
-        digests, cap = eng.merkle(d_leaves, 1, w, log_n, cap_height)
-        return cls(leaves_h, digests, eng.host(cap), cap_height, engine=eng)
+        digests, cap = eng.merkle(d_leaves, 1, w, log_n, cap_height, hash_size=hs)
+        tree = cls(leaves_h, digests, eng.host(cap), cap_height, engine=eng)
+        tree.hasher = hasher
+        return tree
 
     @property
     def leaves(self):

@@ -51,7 +51,16 @@ GATE = '''        #[cfg(feature = "p2hot")]
             return timed!(
                 timing,
                 "p2hot commit",
-                crate::p2hot::commit::<F, C, D>(&crate::p2hot::%s(&%s), rate_bits, cap_height, %s, blinding)
+                crate::p2hot::commit::<F, C, D>(&crate::p2hot::%(slices)s(&%(arg)s), rate_bits, cap_height, %(is_values)s, blinding)
+            );
+        }
+        #[cfg(feature = "p2hot")]
+        if crate::p2hot::applies_keccak_commit::<F, C, D>() {
+            // KeccakGoldilocksConfig: the same LDE with a KeccakHash<25> tree; FRI and the rest stay on the CPU bodies
+            return timed!(
+                timing,
+                "p2hot commit (KeccakHash)",
+                crate::p2hot::commit_keccak::<F, C, D>(&crate::p2hot::%(slices)s(&%(arg)s), rate_bits, cap_height, %(is_values)s, blinding)
             );
         }
 '''
@@ -94,14 +103,14 @@ fn main() {
         let coeffs = timed!(
 ''', '''        fft_root_table: Option<&FftRootTable<F>>,
     ) -> Self {
-''' + GATE % ("value_slices", "values", "true") + '''        let coeffs = timed!(
+''' + GATE % dict(slices="value_slices", arg="values", is_values="true") + '''        let coeffs = timed!(
 '''),
         ('''        fft_root_table: Option<&FftRootTable<F>>,
     ) -> Self {
         let degree = polynomials[0].len();
 ''', '''        fft_root_table: Option<&FftRootTable<F>>,
     ) -> Self {
-''' + GATE % ("coeff_slices", "polynomials", "false") + '''        let degree = polynomials[0].len();
+''' + GATE % dict(slices="coeff_slices", arg="polynomials", is_values="false") + '''        let degree = polynomials[0].len();
 '''),
         ('''        let slice = &self.merkle_tree.leaves[index];
         &slice[..slice.len() - if self.blinding { SALT_SIZE } else { 0 }]
