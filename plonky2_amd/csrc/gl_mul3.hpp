@@ -410,4 +410,54 @@ __device__ __forceinline__ u64 fold1(u64 al, u64 ah) {
     return ra;
 }
 
+// ---- fold3w / fold1w: the same recombination for ANY 64-bit accumulators (the four-round partial-round passes, whose rows reach
+// 2^63.7) ----
+//   1 v_mad_u64_u32 T = ah.hi * -1 + al      carry c1 (weight 2^64 = 2^32 - 1)
+//   2 v_cndmask     e = c1 ? -1 : 0          3 v_mad_u64_u32 T = e * 1 + T   (after a wrap T < (2^32-1)^2: no carry)
+//   4 v_add_co      T.hi += ah.lo            carry c2
+//   5 v_cndmask     e = c2 ? -1 : 0          6 v_mad_u64_u32 r = e * 1 + T   (after a wrap T < 2^64 - 2^32: no carry)
+// Two instructions more than fold3's four; the result is below 2^64 for every al, ah < 2^64.
+#define P2_FW1(P, P0, P1, M, M0, M1, Q, Q0, Q1, C1, C2, a0, a1, b0, b1, r0, r1) "v_mad_u64_u32 " P ", " C1 ", %[" b1 "], -1, %[" a0 "]\n\t"
+#define P2_FW2(P, P0, P1, M, M0, M1, Q, Q0, Q1, C1, C2, a0, a1, b0, b1, r0, r1) "v_cndmask_b32 " M0 ", 0, -1, " C1 "\n\t"
+#define P2_FW3(P, P0, P1, M, M0, M1, Q, Q0, Q1, C1, C2, a0, a1, b0, b1, r0, r1) "v_mad_u64_u32 " P ", " C1 ", " M0 ", 1, " P "\n\t"
+#define P2_FW4 P2_FD2
+#define P2_FW5 P2_FD3
+#define P2_FW6 P2_FD4
+
+// the C statement of one wide row recombination (the emulator's fast path): the same two carries
+__host__ __device__ __forceinline__ u64 fold_row_wide_c(u64 al, u64 ah) {
+    u64 t = (ah >> 32) * 0xFFFFFFFFull + al;
+    t += t < al ? 0xFFFFFFFFull : 0;
+    const u64 u = t + (ah << 32);
+    return u + (u < t ? 0xFFFFFFFFull : 0);
+}
+
+// y[k] = al[k] + ah[k] * 2^32 (mod P), k = 0..2, for any al, ah < 2^64
+__device__ __forceinline__ void fold3w(const u64 al[3], const u64 ah[3], u64 y[3]) {
+    if (!P2_ASM_INTERPRETED()) {
+        for (int k = 0; k < 3; ++k) y[k] = fold_row_wide_c(al[k], ah[k]);
+        return;
+    }
+    u64 ra, rb, rc;
+    P2_ASM(P2_ROW(P2_FW1) P2_ROW(P2_FW2) P2_ROW(P2_FW3) P2_ROW(P2_FW4) P2_ROW(P2_FW5) P2_ROW(P2_FW6),
+           (P2_O([ra0], "=&v", ra), P2_O([rb0], "=&v", rb), P2_O([rc0], "=&v", rc)),
+           (P2_I([xa0], "v", al[0]), P2_I([ya0], "v", (u32)ah[0]), P2_I([ya1], "v", (u32)(ah[0] >> 32)),
+            P2_I([xb0], "v", al[1]), P2_I([yb0], "v", (u32)ah[1]), P2_I([yb1], "v", (u32)(ah[1] >> 32)),
+            P2_I([xc0], "v", al[2]), P2_I([yc0], "v", (u32)ah[2]), P2_I([yc1], "v", (u32)(ah[2] >> 32))),
+           ("v70", "v71", "v72", "v76", "v77", "v78", "v82", "v83", "v84", "s40", "s41", "s44", "s45", "s48", "s49"));
+    y[0] = ra;
+    y[1] = rb;
+    y[2] = rc;
+}
+// one wide row recombination as a single stream, explicit wait states
+__device__ __forceinline__ u64 fold1w(u64 al, u64 ah) {
+    if (!P2_ASM_INTERPRETED()) return fold_row_wide_c(al, ah);
+    u64 ra;
+    P2_ASM(P2_A1(P2_FW1, P2_SA) P2_NOP P2_A1(P2_FW2, P2_SA) P2_A1(P2_FW3, P2_SA) P2_A1(P2_FW4, P2_SA) P2_NOP P2_A1(P2_FW5, P2_SA)
+               P2_A1(P2_FW6, P2_SA),
+           (P2_O([ra0], "=&v", ra)), (P2_I([xa0], "v", al), P2_I([ya0], "v", (u32)ah), P2_I([ya1], "v", (u32)(ah >> 32))),
+           ("v70", "v71", "v72", "s40", "s41"));
+    return ra;
+}
+
 }  // namespace gl

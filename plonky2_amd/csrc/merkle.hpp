@@ -271,7 +271,8 @@ __global__ void field_selftest_kernel(const u64 *a, const u64 *b, size_t count, 
     u64 ok = (gl::canon(rr[1]) == gl::canon(rr[0])) && (gl::canon(rr[2]) == gl::canon(gl::mul(x, x))) ? 0 : 1;
     // the other hand-written streams against the compiler's arithmetic, one flag bit each:
     // 2 = the low-register single stream, 4 = the power-of-two twiddle multiplies of the radix-8 butterflies (ntt.hpp),
-    // 8 / 16 = the MDS row recombinations fold1 / fold3 on accumulators below 2^63, 32 / 64 = the two-stream mul2 / fold2, 128 = gl::mul_add, 256 = gl::mad3, 512 = gl::mul3cf / mul1cf / mul3cg / mul1cg
+    // 8 / 16 = the MDS row recombinations fold1 / fold3 on accumulators below 2^63, 32 / 64 = the two-stream mul2 / fold2, 128 = gl::mul_add, 256 = gl::mad3, 512 = gl::mul3cf / mul1cf / mul3cg / mul1cg,
+    // 1024 = the wide recombinations fold1w / fold3w
     if (gl::canon(gl::mul1_lowregs(x, y)) != gl::canon(gl::mul(x, y))) ok |= 2;
 #define P2_CHK_POW2(S)                                                                                              \
     if (gl::canon(ntt::mul_pow2_asm<S>(x)) != gl::canon(gl::mul(x, (S) < 64 ? 1ull << ((S) & 63) : 0xFFFFFFFFull << (((S) - 64) & 31)))) \
@@ -325,6 +326,14 @@ __global__ void field_selftest_kernel(const u64 *a, const u64 *b, size_t count, 
         for (int k = 0; k < 3; ++k)
             if (gl::canon(r3[k]) != gl::canon(gl::mul(a3[k], b3[k]))) ok |= 512;
         if (gl::canon(gl::mul1cg(x, y)) != gl::canon(gl::mul(x, y)) || gl::canon(gl::mul1cg(y, y)) != gl::canon(gl::mul(y, y))) ok |= 512;
+    }
+    {  // 1024 = the wide row recombinations (gl::fold1w / fold3w) on accumulators up to 2^64 - 1: al = x, ah = y as given
+        const u64 al3[3] = {x, y, x ^ y}, ah3[3] = {y, x, ~x};
+        u64 y3[3];
+        gl::fold3w(al3, ah3, y3);
+        for (int k = 0; k < 3; ++k)
+            if (gl::canon(y3[k]) != gl::canon(gl::add(al3[k], gl::mul(ah3[k], 1ull << 32)))) ok |= 1024;
+        if (gl::canon(gl::fold1w(x, y)) != gl::canon(gl::add(x, gl::mul(y, 1ull << 32)))) ok |= 1024;
     }
     out[2 * count + t] = gl::canon(rr[0]);
     out[5 * count + t] = ok;

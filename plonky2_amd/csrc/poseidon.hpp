@@ -19,7 +19,7 @@
 //    {lo32, hi32} words, seed the two accumulators straight from SGPRs.  In the partial rounds the
 //    constants of the 11 passive words are pushed forward through the (linear) MDS at table-generation
 //    time, so those rounds add a single scalar to word 0 and round 26 absorbs the remainder.
-//  * The partial rounds run three to a dense pass over integer products of the MDS matrix, written with the projection
+//  * The partial rounds run four to a dense pass (three in the last) over integer products of the MDS matrix, written with the projection
 //    D = diag(0, 1, .., 1) (a round REPLACES word 0) so that no field subtraction is needed; their scalars are chain addends too.
 //  * Round loops stay rolled so the kernel body fits the instruction cache (one batch of partial rounds is peeled: it carries
 //    round 26's constant vector).
@@ -305,45 +305,96 @@ constexpr Mat12 mat_drop_col0(const Mat12 &a) {
 P2_LITERAL_QUAL Mat12 MDS1 = mds_matrix();
 P2_LITERAL_QUAL Mat12 MDM = mat_mul(mat_drop_col0(mds_matrix()), mds_matrix());
 P2_LITERAL_QUAL Mat12 MDMDM = mat_mul(mat_drop_col0(mds_matrix()), mat_mul(mat_drop_col0(mds_matrix()), mds_matrix()));
+P2_LITERAL_QUAL Mat12 MDMDMDM = mat_mul(mat_drop_col0(mds_matrix()), MDMDM);  // (MD)^3 M: entries < 2^28.3, rows < 2^31.8
 
-// A full round's MDS and the partial round after it in one dense pass (round 3's linear layer + round 4): with x the state after
-// the full round's S-box layer, u = M x, s = sbox(u[0] + c), the state after the partial round is
-//   y = M (D u + s e0) = (MD) M x + s (M e0)
-// -- one 12-row pass over (MD) M (+1 term per row), one single row for u[0] and one S-box, instead of two 12-row passes.  With it the
-// 1 + 22 applications of M between the two full-round halves take 8 dense passes (this one and seven batches of three) instead of 9.
-// No pending constant on entry or exit (round 3 fuses none; c = the partial round's pushed scalar).
-// c rides the u[0] chain as its starting addend (halves, like every constant here); cn = the NEXT partial round's scalar, fused into
-// row 0 the same way, so that no partial round adds its constant with instructions of its own.
-__device__ __forceinline__ void mds_partial_round(u64 s[12], u64 c, u64 cn) {
+// The four-application pass's rows: (MD)^3 M z + s1 (MD)^2 M e0 + s2 (MD) M e0 + s3 M e0 (+ one constant half).  Each chain
+// multiplies 32-bit halves, so a row is below (coefficient sum) * (2^32 - 1) + 2^32 -- 2^63.72 at the largest row: over 2^63 (hence
+// gl::fold3w) but below 2^64.  Checked here in 64-bit integers, entry by entry from the same products the kernel multiplies by; a
+// fifth application (rows of 2^39.6) does not fit.
+constexpr bool pass4_rows_fit() {
+    const Mat12 m1 = mds_matrix(), md = mat_drop_col0(m1);
+    const Mat12 p1 = mat_mul(md, m1), p2 = mat_mul(md, p1), p3 = mat_mul(md, p2);
+    for (int i = 0; i < 144; ++i)
+        if (p1.v[i] != MDM.v[i] || p2.v[i] != MDMDM.v[i] || p3.v[i] != MDMDMDM.v[i]) return false;
+    for (int r = 0; r < 12; ++r) {
+        u64 sum = (u64)p2.v[12 * r] + p1.v[12 * r] + m1.v[12 * r];
+        for (int c = 0; c < 12; ++c) {
+            u64 e = 0;  // the entry recomputed in 64 bits: the u32 products above must not have truncated
+            for (int k = 0; k < 12; ++k) e += (u64)md.v[12 * r + k] * p2.v[12 * k + c];
+            if (e != p3.v[12 * r + c]) return false;
+            sum += e;
+        }
+        if (sum > (1ull << 32)) return false;  // (sum + 1) * (2^32 - 1) <= 2^64 - 1
+    }
+    return true;
+}
+static_assert(pass4_rows_fit(), "(MD)^3 M: a four-application row would overflow its 64-bit chains");
+
+// Four partial rounds in one dense pass (the algebra of partial_rounds3 below, one round further).  With z the state whose word 0
+// already went through round 0's S-box:
+//   y1[0] = (M z)[0]                                                  s1 = sbox(y1[0] + c1)
+//   y2[0] = ((MD) M z)[0] + s1 M[0][0]                                s2 = sbox(y2[0] + c2)
+//   y3[0] = ((MD)^2 M z)[0] + s1 ((MD) M)[0][0] + s2 M[0][0]          s3 = sbox(y3[0] + c3)
+//   y4    = (MD)^3 M z + s1 ((MD)^2 M e0) + s2 ((MD) M e0) + s3 (M e0)
+// Four rounds cost one 12-row pass (+3 terms per row), three single rows and four S-boxes.  The pass's rows reach 2^63.72
+// (pass4_rows_fit): still two 32x32+64 chains each, recombined by the wide fold (gl::fold3w, two instructions more per row than
+// gl::fold3).  A fifth application does not fit (rows of 2^39.6 * 2^32).  The scalars ride the chains as in partial_rounds3: c1..c3
+// those of this batch's second to fourth round, cn that of the NEXT pass's first round (fused into row 0).
+// FIRST: the pass that starts at round 3's MDS -- z is the state after round 3's full S-box layer (no S-box on word 0 here), c1..c3 are
+// the scalars of partial rounds 4..6: 1 + 22 applications of M between the two full-round halves take 6 dense passes (this one, four
+// batches of four and the three-round tail batch) instead of 8.
+template <bool FIRST = false>
+__device__ __forceinline__ void partial_rounds4(u64 s[12], u64 c1, u64 c2, u64 c3, u64 cn) {
     u32 xl[12], xh[12];
+    const u64 z0 = FIRST ? s[0] : sbox7_asm(s[0]);  // (not FIRST) round 0's scalar is already in s[0]
+    xl[0] = (u32)z0;
+    xh[0] = (u32)(z0 >> 32);
 #pragma unroll
-    for (int i = 0; i < 12; ++i) {
+    for (int i = 1; i < 12; ++i) {
         xl[i] = (u32)s[i];
         xh[i] = (u32)(s[i] >> 32);
     }
-    u64 al = (u32)c, ah = c >> 32;
+    u64 al = (u32)c1, ah = c1 >> 32;
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
         al += (u64)xl[j] * P2_POSEIDON_M1_ROW0[j];
         ah += (u64)xh[j] * P2_POSEIDON_M1_ROW0[j];
     }
     const u64 s1 = sbox7_asm(gl::fold1(al, ah));
-    const u32 sl = (u32)s1, sh = (u32)(s1 >> 32);
+    const u32 s1l = (u32)s1, s1h = (u32)(s1 >> 32);
+    al = (u64)s1l * MDS1.v[0] + (u32)c2;
+    ah = (u64)s1h * MDS1.v[0] + (c2 >> 32);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        al += (u64)xl[j] * MDM.v[j];
+        ah += (u64)xh[j] * MDM.v[j];
+    }
+    const u64 s2 = sbox7_asm(gl::fold1(al, ah));
+    const u32 s2l = (u32)s2, s2h = (u32)(s2 >> 32);
+    al = (u64)s1l * MDM.v[0] + (u64)s2l * MDS1.v[0] + (u32)c3;
+    ah = (u64)s1h * MDM.v[0] + (u64)s2h * MDS1.v[0] + (c3 >> 32);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        al += (u64)xl[j] * MDMDM.v[j];
+        ah += (u64)xh[j] * MDMDM.v[j];
+    }
+    const u64 s3 = sbox7_asm(gl::fold1(al, ah));  // row 0 of (MD)^2 M: below 2^25 * 2^32
+    const u32 s3l = (u32)s3, s3h = (u32)(s3 >> 32);
 #pragma unroll
     for (int g = 0; g < 12; g += 3) {
         u64 bl[3], bh[3], y[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int i = g + t;
-            bl[t] = (u64)sl * MDS1.v[12 * i] + (i == 0 ? (u64)(u32)cn : 0);
-            bh[t] = (u64)sh * MDS1.v[12 * i] + (i == 0 ? cn >> 32 : 0);
+            bl[t] = (u64)s1l * MDMDM.v[12 * i] + (u64)s2l * MDM.v[12 * i] + (u64)s3l * MDS1.v[12 * i] + (i == 0 ? (u64)(u32)cn : 0);
+            bh[t] = (u64)s1h * MDMDM.v[12 * i] + (u64)s2h * MDM.v[12 * i] + (u64)s3h * MDS1.v[12 * i] + (i == 0 ? cn >> 32 : 0);
 #pragma unroll
             for (int j = 0; j < 12; ++j) {
-                bl[t] += (u64)xl[j] * MDM.v[12 * i + j];
-                bh[t] += (u64)xh[j] * MDM.v[12 * i + j];
+                bl[t] += (u64)xl[j] * MDMDMDM.v[12 * i + j];
+                bh[t] += (u64)xh[j] * MDMDMDM.v[12 * i + j];
             }
         }
-        gl::fold3(bl, bh, y);
+        gl::fold3w(bl, bh, y);
         s[g] = y[0];
         s[g + 1] = y[1];
         s[g + 2] = y[2];
@@ -357,9 +408,9 @@ __device__ __forceinline__ void mds_partial_round(u64 s[12], u64 c, u64 cn) {
 //   y3    = (MD)(MD) M z + s1 ((MD) M e0) + s2 (M e0)
 // and the integer products of the MDS matrix stay small ((MD)(MD) M <= M^3 < 2^21 per entry, < 2^25 per row), so a row is still two
 // 32x32+64 multiply-add chains (accumulators < 2^58): three rounds cost one 12-row pass (+2 terms per row), two single rows and three
-// S-boxes instead of three 12-row passes.  The matrix entries are s_mov_b32 literals in the instruction stream (P2_LITERAL_QUAL).  A
-// fourth power does not pay: the rows of M^4 sum to 1.04 * 2^32 (the chains would overflow); splitting off its near-constant part
-// t * J costs a scalar t * sum(z) added to all 24 accumulators, and the measured gain was 1 %.  The rounds' scalar constants
+// S-boxes instead of three 12-row passes.  The matrix entries are s_mov_b32 literals in the instruction stream (P2_LITERAL_QUAL).  (The
+// plain power M^4 would not fit -- its rows sum to 1.04 * 2^32 -- but the column-0-dropped product (MD)^3 M does: partial_rounds4
+// above runs four rounds a pass; this three-round form is the tail batch.)  The rounds' scalar constants
 // (P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 r]) ride the chains as starting addends: c1, c2 those of this batch's second and third round,
 // cn that of the NEXT pass's first round (fused into row 0); this batch's first is already in s[0].
 // TAIL (the last batch): cv = the constant VECTOR of the full round that follows, fused into all twelve rows (cn unused).
@@ -415,7 +466,8 @@ __device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, u64 c
 
 #ifndef P2HOT_TAIL_BATCH
 #define P2HOT_TAIL_BATCH 1  // 1: the last batch of partial rounds is its own copy with round 26's constant vector fused into its rows (eleven
-                            // 4-instruction additions less per permutation: -0.3 % cycles, profiles/r06_partial_rounds_ab.txt); 0: one rolled loop
+                            // 4-instruction additions less per permutation: -0.3 % cycles, profiles/r06_partial_rounds_ab.txt); 0: the vector is
+                            // added after the last batch
 #endif
 // the permutation; output words are NOT canonicalised (callers canonicalise what they emit).
 // Round r: ARK(r) was already added by the previous MDS (or up front for r = 0); S-box; MDS + ARK(r+1).
@@ -432,29 +484,32 @@ __device__ inline void permute(u64 s[12], unsigned out_groups = 0xFu, int out_si
         sbox_layer(s);
         mds_layer(s, RC_SPLIT + 24 * (round + 1));
     }
-    // round 3's S-box layer; its MDS and partial round 4 in ONE dense pass (M^2: mds_partial_round); no constant is fused into
+    // round 3's S-box layer; its MDS and partial rounds 4..6 in ONE dense pass (partial_rounds4<true>); no constant is fused into
     // round 3's MDS -- the batched partial rounds add their scalars themselves (the passive part of the partial-round constants
     // is pushed forward through the MDS at table-generation time, see the generator)
     sbox_layer(s);
-    mds_partial_round(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 4], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 5]);
-    round = 5;
-    // partial rounds 5..25 in seven batches of three (each batch's first scalar was fused into row 0 of the pass before it).  The
-    // constant vector of round 26 (which absorbed the pushed remainder) rides the LAST batch's rows; that batch is its own copy of the
-    // code, outside the rolled loop: fused into the loop's accumulators the vector would be 44 more live SGPRs in EVERY batch
-    // (measured: 96 v_readlane per batch of SGPR spill traffic, +4 % instructions)
+    partial_rounds4<true>(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 4], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 5],
+                          P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 6], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 7]);
+    round = 7;
+    // partial rounds 7..22 in four batches of four (each batch's first scalar was fused into row 0 of the pass before it), 23..25 in
+    // one batch of three.  The constant vector of round 26 (which absorbed the pushed remainder) rides that LAST batch's rows; it is its
+    // own copy of the code, outside the rolled loop: fused into the loop's accumulators the vector would be 44 more live SGPRs in EVERY
+    // batch (measured: 96 v_readlane per batch of SGPR spill traffic, +4 % instructions)
 #pragma unroll 1
-    for (int k = 0; k < (P2HOT_TAIL_BATCH ? 6 : 7); ++k, round += 3)
-        partial_rounds3(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 1)], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 2)],
-                        P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 3)]);  // the last batch's cn is round 26's word 0
+    for (int k = 0; k < 4; ++k, round += 4)
+        partial_rounds4(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 1)], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 2)],
+                        P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 3)], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 4)]);
     const u32 z26 = opaque_zero();
     if (P2HOT_TAIL_BATCH) {
         partial_rounds3<true>(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 24], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 25], 0,
                               P2_POSEIDON_PUSHED_ROUND_CONSTANTS + 12 * 26 + z26);
-        round = 26;
     } else {
+        partial_rounds3(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 24], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 25],
+                        P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 26]);
 #pragma unroll
-        for (int i = 1; i < 12; ++i) s[i] = ark(s[i], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * round + i + z26]);
+        for (int i = 1; i < 12; ++i) s[i] = ark(s[i], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 26 + i + z26]);
     }
+    round = 26;
 #pragma unroll 1
     for (int k = 0; k < 3; ++k, ++round) {
         sbox_layer(s);
