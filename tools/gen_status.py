@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 ROWS = [
     ("a1", "Goldilocks add / sub / mul / reduce128", "test_parity.py::test_field_ops_edge_grid", None),
-    ("a2-a5", "fft_root_table, fft_classic (+ zero tail), ifft, coset LDE", "test_parity.py::test_fft_ifft_vs_oracle, ::test_coset_ifft_vs_oracle, ::test_coset_lde_vs_oracle_and_naive", "ntt"),
+    ("a2-a5", "fft_root_table, fft_classic (+ zero tail), ifft, coset LDE", "test_parity.py::test_fft_ifft_vs_oracle, ::test_coset_ifft_vs_oracle, ::test_coset_lde_vs_oracle_and_naive; test_ntt_plans.py (every pass plan of P2HOT_NTT_STRIDED_BITS 6/7/10/11 to 2^25, coset LDE with zloop / bit-reversed source / staged tables, tune modes, vs tests/ntt_ref.py; the limb unit's bounds restated)", "ntt"),
     ("a6", "PolynomialBatch::lde_values (+ salts)", "test_parity.py::test_salted_commit_vs_oracle", None),
     ("a7-a8", "transpose, reverse_index_bits", "test_parity.py::test_transpose, ::test_reverse_index_bits_reference_table; test_async_leaves.py (natural-order host copy)", "bitrev"),
     ("a9-a12", "Poseidon permutation, sponge, hash_or_noop, two_to_one", "test_parity.py::test_poseidon_reference_kats (the 4 reference KATs), ::test_poseidon_random_vs_oracle, ::test_poseidon_edge_states_vs_oracle, ::test_hash_no_pad_and_two_to_one", "hash"),
