@@ -10,7 +10,13 @@ tree) over one synthetic batch of trace columns, inputs already resident in HBM:
              RCCL all-gather of digests/cap.
 value = W * N_total / t / 1e9 (GFE/s, whole job).  One JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--width 135] [--no-cpu-baseline] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps (the cap of each checked against the oracle's golden of the shape), writes
+--dump-outputs and prints the line; the roofline and per-kernel figures come from those same steps.  --full adds what takes
+runs of its own: at --gpus 1 the driver-timed lines of the other BASELINE shapes and per-proof paths (`other_configs`,
+--no-extra skips them) and the CPU baseline (--no-cpu-baseline skips it); at --gpus N the strong-scaling companion and the
+per-proof path over a p2hot_group.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--width 135] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -822,14 +828,19 @@ def main():
     ap.add_argument("--rate-bits", type=int, default=3)
     ap.add_argument("--cap-height", type=int, default=4)
     ap.add_argument("--strong", action="store_true", help="strong scaling: 2^log_n rows in TOTAL (the C3 commit split over the GPUs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra driver-timed lines of the other BASELINE shapes")
-    ap.add_argument("--extra-only", default=None, help="tooling: only this group of extra lines (host)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also what takes runs of its own: the CPU baseline and the other BASELINE shapes "
+                         "(--gpus 1), the strong-scaling companion and the per-proof path over a p2hot_group (--gpus N)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra driver-timed lines of the other BASELINE shapes")
+    ap.add_argument("--extra-only", default=None, help="tooling, with --full: only this group of extra lines (host, path)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one computed (coefficients, LDE, digests, cap) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.extra_only and not args.full:
+        ap.error("--extra-only selects among the lines of --full")
 
     # `python bench.py --gpus N` with no launcher around it: start the N ranks ourselves (one process per GPU under
     # torch.distributed.run, rendezvous on 127.0.0.1), pass the child's JSON line and exit code through
@@ -1048,10 +1059,13 @@ def main():
         rank_rows = [None] * world
         dist.all_gather_object(rank_rows, mine)
 
-    # the strong-scaling companion of a weak-scaling run: the SAME total size at every --gpus (2^log_n rows in all: the C3 wires
+    # --full at --gpus N: the per-proof path over a p2hot_group once the line is assembled (rank 0 drives every GPU, see below)
+    group_path = world > 1 and args.full and os.environ.get("P2HOT_BENCH_NO_GROUP_PATH") != "1"
+
+    # the strong-scaling companion of a weak-scaling run (--full): the SAME total size at every --gpus (2^log_n rows in all: the C3 wires
     # commit split over the ranks), timed and cap-checked the same way on the same communicator, reported under "strong_scaling"
     strong = None
-    if world > 1 and not args.strong and os.environ.get("P2HOT_BENCH_NO_STRONG") != "1":
+    if world > 1 and args.full and not args.strong and os.environ.get("P2HOT_BENCH_NO_STRONG") != "1":
         del cols
         try:  # (a shape this world size cannot shard is the same ValueError on every rank: the companion is dropped, the line stays)
             job2, cols2 = make_job(args.log_n, comm=job.comm)
@@ -1119,14 +1133,14 @@ def main():
             "commit_hbm_frac": ab["total"] / world / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
             **({"dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {}),
         }
-        if world == 1 and not args.no_extra and not emu:
+        if world == 1 and args.full and not args.no_extra and not emu:
             del job, cols
             torch.cuda.empty_cache()
             out["other_configs"] = other_configs(eng, torch, only=args.extra_only)
-        if world == 1 and not args.no_cpu_baseline and not emu:
+        if world == 1 and args.full and not args.no_cpu_baseline and not emu:
             out["cpu_baseline"] = cpu_baseline(W, log_n, rb, cap, golden_cap=g["cap"] if g else None)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-        if world > 1 and os.environ.get("P2HOT_BENCH_NO_GROUP_PATH") != "1":
+        if group_path:
             # (the other ranks have released their devices and wait on the host for the store key set below)
             job.comm.close()
             del job
@@ -1134,7 +1148,7 @@ def main():
                 torch.cuda.empty_cache()
             out["group_per_proof_path"] = group_per_proof_path(eng, torch, world, emu, device_sync)
         print(json.dumps(out))
-    if dist and world > 1 and os.environ.get("P2HOT_BENCH_NO_GROUP_PATH") != "1":
+    if dist and group_path:
         # the per-proof path over a p2hot_group is ONE process driving every GPU (rank 0 above): the other ranks free their device
         # memory and wait on the HOST (the rendezvous store; a device-side barrier would spin on the GPUs rank 0 is using)
         store = torch.distributed.distributed_c10d._get_default_store()

@@ -2,7 +2,8 @@
 bench.py starts its own ranks (torch.distributed.run on 127.0.0.1), forwards rank 0's JSON line and the exit code.  Here the
 ranks sit on the kernel-source emulator and its fake RCCL (P2HOT_BENCH_EMU=1: the test tier's switch, refused nowhere else),
 so the whole front door -- launcher, rank plumbing, in-library RCCL communicator, preflight, sharded commit, the cap check
-against the oracle's golden of the 2-rank shape, the strong-scaling companion, the JSON contract -- runs in the CPU tier."""
+against the oracle's golden of the 2-rank shape, the JSON contract, and with --full the strong-scaling companion -- runs in the
+CPU tier."""
 import json
 import os
 import subprocess
@@ -30,7 +31,7 @@ def _one_json_line(stdout):
 
 
 def test_bench_gpus_2_launches_its_own_ranks():
-    r = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "6")
+    r = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "6", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["emulated"] is True
@@ -47,10 +48,10 @@ def test_bench_gpus_2_launches_its_own_ranks():
 
 
 def test_bench_gpus_2_adds_the_per_proof_path_over_the_group():
-    """behind world > 1: one `group_per_proof_path` record -- the per-proof path as ONE process driving both (emulated) devices
+    """behind world > 1 and --full: one `group_per_proof_path` record -- the per-proof path as ONE process driving both (emulated) devices
     (p2hot_group: four sharded commits from host columns, p2hot_group_eval_openings, p2hot_group_prove_openings), on the k12
     instance here, checked against the same oracle record the single-context path is (tests/golden/path_goldens.json)"""
-    r = _bench("--gpus", "2", "--steps", "1", "--warmup", "0", "--log-n", "6", timeout=1500,
+    r = _bench("--gpus", "2", "--steps", "1", "--warmup", "0", "--log-n", "6", "--full", timeout=1500,
                env_extra={"P2HOT_BENCH_NO_GROUP_PATH": "0", "P2HOT_BENCH_GROUP_PATH": "per_proof_path_k12", "P2HOT_BENCH_NO_STRONG": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json_line(r.stdout)
@@ -65,7 +66,7 @@ def test_bench_gpus_2_adds_the_per_proof_path_over_the_group():
 def test_bench_gpus_8_launches_eight_ranks():
     """the driver's `python bench.py --gpus 8` on the day an 8-GPU node exists: eight ranks on eight emulated devices, the same
     2^7-row shape as eight LDE cosets (one per rank: C5's arrangement), the cap of every step = the oracle's golden"""
-    r = _bench("--gpus", "8", "--steps", "1", "--warmup", "1", "--log-n", "4", timeout=900)
+    r = _bench("--gpus", "8", "--steps", "1", "--warmup", "1", "--log-n", "4", "--full", timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json_line(r.stdout)
     assert d["n_gpus"] == 8 and d["cap_checked"] is True and [row["rank"] for row in d["ranks"]] == list(range(8))
@@ -89,6 +90,20 @@ def test_a_failed_rccl_preflight_falls_back_to_the_launchers_communicator():
     r = _bench("--gpus", "2", "--steps", "1", "--warmup", "0", "--log-n", "6",
                env_extra={"P2HOT_BENCH_EMU_FAIL_PREFLIGHT": "1", "P2HOT_EMU_RCCL_TIMEOUT_MS": "1500", "P2HOT_BENCH_NO_FALLBACK": "1"})
     assert r.returncode != 0 and "bench preflight" in (r.stderr + r.stdout)
+
+
+def test_a_plain_multi_gpu_run_is_the_headline_alone():
+    """without --full a --gpus N run times its steps and prints the line: no strong-scaling companion, no per-proof path over
+    the group (both asked for here, so only the missing --full leaves them out); the cap of every timed step is still checked"""
+    r = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "6",
+               env_extra={"P2HOT_BENCH_NO_GROUP_PATH": "0", "P2HOT_BENCH_GROUP_PATH": "per_proof_path_k12"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_json_line(r.stdout)
+    assert d["n_gpus"] == 2 and d["steps"] == 2 and d["cap_checked"] is True and d["caps_checked"] == 2
+    assert [row["rank"] for row in d["ranks"]] == [0, 1]
+    assert "strong_scaling" not in d and "group_per_proof_path" not in d
+    r = _bench("--gpus", "1", "--steps", "1", "--log-n", "7", "--extra-only", "host")
+    assert r.returncode != 0 and "--full" in r.stderr
 
 
 def test_bench_gpus_1_needs_no_launcher_either():

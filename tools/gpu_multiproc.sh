@@ -4,5 +4,5 @@
 # usage: tools/gpu_multiproc.sh N [log_n per rank, default 20] [extra bench args]
 cd "${GRAFT_REPO_ROOT:-/root/repo}" && mkdir -p gpurun_out
 N=${1:-2}; LOGN=${2:-20}; shift; shift
-P2HOT_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus "$N" --steps 1 --warmup 1 --log-n "$LOGN" "$@" \
+P2HOT_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus "$N" --steps 1 --warmup 1 --log-n "$LOGN" --full "$@" \
     > "gpurun_out/multiproc_$N.json" 2> "gpurun_out/multiproc_$N.err"; echo "multiproc N=$N rc=$?"; tail -c 600 "gpurun_out/multiproc_$N.json"

@@ -14,7 +14,7 @@ tests)
 ubench)
   timeout 120 ./tools/ubench > gpurun_out/ubench.log 2>&1; cat gpurun_out/ubench.log ;;
 bench)
-  timeout 900 python bench.py --steps 10 --warmup 2 > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "bench rc=$?"; cat gpurun_out/bench.json; tail -3 gpurun_out/bench.err
+  timeout 900 python bench.py --full --steps 10 --warmup 2; echo "bench rc=$?"
   lscpu | egrep "Model name|^CPU\(s\)|Socket|Thread" > gpurun_out/lscpu.txt ;;
 prof)
   ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/gpurun_out/prof" -o p2hot -- python "$OLDPWD/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-extra > "$OLDPWD/gpurun_out/prof_bench.json" 2> "$OLDPWD/gpurun_out/prof.err" ); echo "prof rc=$?"
