@@ -271,7 +271,7 @@ __global__ void field_selftest_kernel(const u64 *a, const u64 *b, size_t count, 
     u64 ok = (gl::canon(rr[1]) == gl::canon(rr[0])) && (gl::canon(rr[2]) == gl::canon(gl::mul(x, x))) ? 0 : 1;
     // the other hand-written streams against the compiler's arithmetic, one flag bit each:
     // 2 = the low-register single stream, 4 = the power-of-two twiddle multiplies of the radix-8 butterflies (ntt.hpp),
-    // 8 / 16 = the MDS row recombinations fold1 / fold3 on accumulators below 2^63, 32 / 64 = the two-stream mul2 / fold2, 128 = gl::mul_add, 256 = gl::mad3, 512 = gl::mul3cf / mul1cf / mul3cg / mul1cg,
+    // 8 / 16 = the MDS row recombinations fold1 / fold3 on accumulators below 2^63, 32 = the two-stream mul2 (64: reserved, never set), 128 = gl::mul_add, 256 = gl::mad3, 512 = gl::mul3cg / mul1cg,
     // 1024 = the wide recombinations fold1w / fold3w
     if (gl::canon(gl::mul1_lowregs(x, y)) != gl::canon(gl::mul(x, y))) ok |= 2;
 #define P2_CHK_POW2(S)                                                                                              \
@@ -295,11 +295,6 @@ __global__ void field_selftest_kernel(const u64 *a, const u64 *b, size_t count, 
         u64 r2[2];
         gl::mul2(a2, b2, r2);
         if (gl::canon(r2[0]) != gl::canon(gl::mul(x, y)) || gl::canon(r2[1]) != gl::canon(gl::mul(a2[1], x))) ok |= 32;
-        const u64 l2[2] = {x >> 1, y >> 1}, h2[2] = {y >> 1, x >> 1};
-        u64 f2[2];
-        gl::fold2(l2, h2, f2);
-        for (int k = 0; k < 2; ++k)
-            if (gl::canon(f2[k]) != gl::canon(gl::add(l2[k], gl::mul(h2[k], 1ull << 32)))) ok |= 64;
     }
     // 128 = the fused multiply-add (gl::mul_add: the addend rides the multiply-add chain), with addends up to 2^64 - 1
     if (gl::canon(gl::mul_add(x, y, x ^ y)) != gl::canon(gl::add(gl::mul(x, y), x ^ y)) || gl::canon(gl::mul_add(y, x, ~0ull)) != gl::canon(gl::add(gl::mul(x, y), ~0ull)) ||
@@ -312,17 +307,10 @@ __global__ void field_selftest_kernel(const u64 *a, const u64 *b, size_t count, 
         for (int k = 0; k < 3; ++k)
             if (gl::canon(r3[k]) != gl::canon(gl::add(gl::mul(a3[k], b3[k]), c3[k]))) ok |= 256;
     }
-    {  // 512 = the carry-free multiply streams of the Poseidon S-boxes (gl::mul3cf / mul1cf and mul3cg / mul1cg: partial products chained through the addend)
+    {  // 512 = the carry-free multiply streams of the Poseidon S-boxes (gl::mul3cg / mul1cg: partial products chained through the addend)
         const u64 a3[3] = {x, y, x ^ 0x9E3779B97F4A7C15ull}, b3[3] = {y, y, x};
         u64 r3[3];
-        gl::mul3cf(a3, b3, r3);
-        for (int k = 0; k < 3; ++k)
-            if (gl::canon(r3[k]) != gl::canon(gl::mul(a3[k], b3[k]))) ok |= 512;
-        if (gl::canon(gl::mul1cf(x, y)) != gl::canon(gl::mul(x, y)) || gl::canon(gl::mul1cf(y, y)) != gl::canon(gl::mul(y, y))) ok |= 512;
         gl::mul3cg(a3, b3, r3);
-        for (int k = 0; k < 3; ++k)
-            if (gl::canon(r3[k]) != gl::canon(gl::mul(a3[k], b3[k]))) ok |= 512;
-        gl::mul3ch(a3, b3, r3);
         for (int k = 0; k < 3; ++k)
             if (gl::canon(r3[k]) != gl::canon(gl::mul(a3[k], b3[k]))) ok |= 512;
         if (gl::canon(gl::mul1cg(x, y)) != gl::canon(gl::mul(x, y)) || gl::canon(gl::mul1cg(y, y)) != gl::canon(gl::mul(y, y))) ok |= 512;

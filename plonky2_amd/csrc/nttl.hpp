@@ -28,44 +28,10 @@ using gl::u32;
 using gl::u64;
 
 constexpr int TILE_LOG = 12;
-constexpr int NT = 512;  // threads per TILE (a workgroup is NT * DUAL threads: DUAL = 2 transforms two tiles side by side)
-// P2HOT_LIMB_DUAL: also build the two-tiles-per-workgroup form (1024 threads = 16 waves = the CU's four waves per SIMD in ONE barrier
-// domain) and P2HOT_LIMB_PHASE: separate a round's butterfly phase (plain 32-bit adds) from its conversion phase (multiply-adds)
-// by workgroup barriers, so that every wave of a SIMD is in the same phase at the same time.  Why: profiles/r06_ubench_cheap.txt --
-// the cheap integer class issues two instructions per 4-cycle slot only while EVERY resident wave offers one.
-#ifndef P2HOT_LIMB_DUAL
-#define P2HOT_LIMB_DUAL 0
-#endif
-#ifndef P2HOT_LIMB_PHASE
-#define P2HOT_LIMB_PHASE 0
-#endif
-constexpr bool LIMB_PHASE = P2HOT_LIMB_PHASE != 0;
-#ifndef P2HOT_LIMB_MIN_WAVES
-#define P2HOT_LIMB_MIN_WAVES 4
-#endif
-#ifndef P2HOT_LIMB_DIRECT_CONTIG
-#define P2HOT_LIMB_DIRECT_CONTIG 0
-#endif
-#ifndef P2HOT_LIMB_DEFER
-#define P2HOT_LIMB_DEFER 1
-#endif
-#ifndef P2HOT_LIMB_MUL3
-#define P2HOT_LIMB_MUL3 1
-#endif
-constexpr bool LIMB_DEFER = P2HOT_LIMB_DEFER != 0;  // a borrowed first-round table defers its small factor to a later round's table
-#ifndef P2HOT_LIMB_MULCF
-#define P2HOT_LIMB_MULCF 2  // the passes' general multiplies (coset scale, inter-pass twiddle): 2 = gl::mul3cg / mul1cg, the 14-instruction stream with 3
-#endif                      // co-issued moves the Poseidon S-boxes run (same count as gl::mul3; LDE strided pass -2.8 % cycles under PMC, 4.31 - 4.34
-                            // against 4.35 ms: profiles/r06_sbox_hybrid_ab.txt); 1 = gl::mul3cf (16 instructions: measured no faster here); 0 = gl::mul3
-#ifndef P2HOT_LIMB_FOLD3
-#define P2HOT_LIMB_FOLD3 0
-#endif
-constexpr bool LIMB_FOLD3 = P2HOT_LIMB_FOLD3 != 0;  // a unit's conversions fold their accumulator pairs three at a time (gl::fold3): measured
-                                                    // SLOWER (LDE contiguous pass 4.69 vs 4.56 ms: 116 VGPRs instead of 101), and so did
-                                                    // pairs (= 2: 4.83 vs 4.71 ms, 114 VGPRs); off
-constexpr bool LIMB_MUL3 = P2HOT_LIMB_MUL3 != 0;    // independent general multiplies of a unit go through gl::mul3 streams
-constexpr bool LIMB_DIRECT_CONTIG = P2HOT_LIMB_DIRECT_CONTIG != 0;  // contiguous pass: store the last round's outputs from registers
-constexpr int LIMB_MIN_WAVES = P2HOT_LIMB_MIN_WAVES;  // waves per SIMD the register allocation must allow (4: <= 128 VGPRs)
+constexpr int NT = 512;  // threads per workgroup = per tile
+constexpr int LIMB_MIN_WAVES = 4;  // waves per SIMD the register allocation must allow (4: <= 128 VGPRs)
+// (Variants that were built, measured and dropped -- two tiles per workgroup, phase barriers, grouped folds, direct stores of the
+// contiguous pass, other multiply streams: DESIGN.md section 8 and profiles/.)
 
 // The tile's place in LDS.  ntt.hpp pads one word per 16 (pad_idx); under the per-instruction banking of gfx950 -- ds_read_b64: two
 // groups of 32 lanes over 32 eight-byte banks, ds_write_b64: four groups of 16 lanes over 16 -- that padding itself costs a second
@@ -75,17 +41,10 @@ constexpr int LIMB_MIN_WAVES = P2HOT_LIMB_MIN_WAVES;  // waves per SIMD the regi
 // which is conflict-free for every access pattern of every tile shape but one (2^10 x 2^2: 1.11 cycles per group), no padding
 // words, and -- being linear -- lets a unit's 2^P addresses be ONE swizzled base XOR compile-time constants: the base and the
 // q-offsets occupy disjoint bits, so swz(base + off_q) = swz(base) ^ swz(off_q).  (tools/lds_conflicts.py is the model.)
-#ifndef P2HOT_LIMB_SWZ
-#define P2HOT_LIMB_SWZ 1
-#endif
-constexpr bool LIMB_SWZ = P2HOT_LIMB_SWZ != 0;
-__host__ __device__ constexpr unsigned swz(unsigned i) { return LIMB_SWZ ? i ^ (((i >> 2) ^ (i >> 3)) & 31u) : i + (i >> 4); }
-// the tile word of base + off for DISJOINT bit sets base / off (off a compile-time constant at every call site)
-__device__ __forceinline__ unsigned tix(unsigned sbase, unsigned base, unsigned off) {
-    if constexpr (LIMB_SWZ) return sbase ^ swz(off);
-    return swz(base + off);
-}
-constexpr unsigned TILE_WORDS = LIMB_SWZ ? (1u << TILE_LOG) : ntt::TILE_WORDS_PADDED;
+__host__ __device__ constexpr unsigned swz(unsigned i) { return i ^ (((i >> 2) ^ (i >> 3)) & 31u); }
+// the tile word of base + off for DISJOINT bit sets base / off (off a compile-time constant at every call site); sbase = swz(base)
+__device__ __forceinline__ unsigned tix(unsigned sbase, unsigned off) { return sbase ^ swz(off); }
+constexpr unsigned TILE_WORDS = 1u << TILE_LOG;
 
 struct L4 {
     u32 l[4];  // signed limbs, two's complement
@@ -191,77 +150,24 @@ __host__ __device__ __forceinline__ void dft_limbs(L4 (&x)[1 << P]) {
 
 // sum_i L_i * W_i (mod P) for non-negative limbs L_i < 2^29 and W_i < 2^64: two 4-term multiply-add chains (the value is
 // al + ah * 2^32, both below 2^63) + one fold
-struct Acc {
-    u64 al, ah;
-};
-__device__ __forceinline__ Acc convmul_acc(const L4 &v, u64 w0, u64 w1, u64 w2, u64 w3) {
-    Acc r;
-    r.al = (u64)v.l[0] * (u32)w0;
-    r.ah = (u64)v.l[0] * (u32)(w0 >> 32);
-    r.al += (u64)v.l[1] * (u32)w1;
-    r.ah += (u64)v.l[1] * (u32)(w1 >> 32);
-    r.al += (u64)v.l[2] * (u32)w2;
-    r.ah += (u64)v.l[2] * (u32)(w2 >> 32);
-    r.al += (u64)v.l[3] * (u32)w3;
-    r.ah += (u64)v.l[3] * (u32)(w3 >> 32);
-    return r;
-}
 __device__ __forceinline__ u64 convmul(const L4 &v, u64 w0, u64 w1, u64 w2, u64 w3) {
-    const Acc r = convmul_acc(v, w0, w1, w2, w3);
-    return gl::fold1(r.al, r.ah);
+    u64 al = (u64)v.l[0] * (u32)w0;
+    u64 ah = (u64)v.l[0] * (u32)(w0 >> 32);
+    al += (u64)v.l[1] * (u32)w1;
+    ah += (u64)v.l[1] * (u32)(w1 >> 32);
+    al += (u64)v.l[2] * (u32)w2;
+    ah += (u64)v.l[2] * (u32)(w2 >> 32);
+    al += (u64)v.l[3] * (u32)w3;
+    ah += (u64)v.l[3] * (u32)(w3 >> 32);
+    return gl::fold1(al, ah);
 }
 
 // the same with W_i = B^i (no twiddle: frequency 0, or the last round of a tile)
-__device__ __forceinline__ Acc conv_unit_acc(const L4 &v) {
-    Acc r;
-    r.al = (u64)v.l[3] * (u32)B3 + v.l[0];
-    r.al += (u64)v.l[1] << 24;
-    r.ah = (u64)v.l[3] * (u32)(B3 >> 32) + ((u64)v.l[2] << 16);
-    return r;
-}
 __device__ __forceinline__ u64 conv_unit(const L4 &v) {
-    const Acc r = conv_unit_acc(v);
-    return gl::fold1(r.al, r.ah);
-}
-
-// y[q] = fold(acc_of(q)), q < N, three rows per interleaved gl::fold3 stream (then two, then one): the single-stream fold
-// stalls its wave two wait states per row, and a unit has 2^P independent rows
-template <int N, class AccF>
-__device__ __forceinline__ void fold_groups(AccF acc_of, u64 (&y)[N]) {
-    if constexpr (P2HOT_LIMB_FOLD3 == 2) {  // pairs: two rows per gl::fold2 stream (two accumulator pairs alive instead of three)
-#pragma unroll
-        for (int q = 0; q + 2 <= N; q += 2) {
-            const Acc a0 = acc_of(q), a1 = acc_of(q + 1);
-            const u64 al[2] = {a0.al, a1.al}, ah[2] = {a0.ah, a1.ah};
-            u64 r[2];
-            gl::fold2(al, ah, r);
-            y[q] = r[0], y[q + 1] = r[1];
-        }
-        if constexpr (N & 1) {
-            const Acc a0 = acc_of(N - 1);
-            y[N - 1] = gl::fold1(a0.al, a0.ah);
-        }
-        return;
-    }
-    constexpr int N3 = N / 3 * 3;
-#pragma unroll
-    for (int q = 0; q < N3; q += 3) {
-        const Acc a0 = acc_of(q), a1 = acc_of(q + 1), a2 = acc_of(q + 2);
-        const u64 al[3] = {a0.al, a1.al, a2.al}, ah[3] = {a0.ah, a1.ah, a2.ah};
-        u64 r[3];
-        gl::fold3(al, ah, r);
-        y[q] = r[0], y[q + 1] = r[1], y[q + 2] = r[2];
-    }
-    if constexpr (N - N3 == 2) {
-        const Acc a0 = acc_of(N3), a1 = acc_of(N3 + 1);
-        const u64 al[2] = {a0.al, a1.al}, ah[2] = {a0.ah, a1.ah};
-        u64 r[2];
-        gl::fold2(al, ah, r);
-        y[N3] = r[0], y[N3 + 1] = r[1];
-    } else if constexpr (N - N3 == 1) {
-        const Acc a0 = acc_of(N3);
-        y[N3] = gl::fold1(a0.al, a0.ah);
-    }
+    u64 al = (u64)v.l[3] * (u32)B3 + v.l[0];
+    al += (u64)v.l[1] << 24;
+    const u64 ah = (u64)v.l[3] * (u32)(B3 >> 32) + ((u64)v.l[2] << 16);
+    return gl::fold1(al, ah);
 }
 
 struct LimbPassArgs {
@@ -313,7 +219,7 @@ constexpr bool round_borrows(int log_r, int r) { return round_log_rb(log_r, r) -
 // w_{Rb}^(a * k) * w_{R}^(a * k0), one slab per k0 (wave-uniform: a wave owns one first-round block), frequency 0 included.
 // For the 4096-point tile (rounds 3+3+3+3): round 2, 8 * 8 * 8 entries = 16 KiB, and round 0 loses its second multiply.
 constexpr int absorb_round(int log_r) {  // the round that absorbs, or -1: then round 0 keeps its second multiply
-    if (!LIMB_DEFER || !round_borrows(log_r, 0)) return -1;
+    if (!round_borrows(log_r, 0)) return -1;
     for (int r = 1; r < n_rounds(log_r); ++r)
         if (round_log_rb(log_r, r) - round_bits(log_r, r) == round_bits(log_r, 0)) return r;
     return -1;
@@ -333,40 +239,31 @@ constexpr int round_table_off(int log_r, int r) {
 constexpr int limb_tables_w2(int log_r) { return round_table_off(log_r, n_rounds(log_r)); }
 constexpr int UFAC_WORDS = 64;  // u[a * 8 + k], a < 8, k < 8 (only round 0 ever borrows)
 constexpr bool uses_ufac(int log_r) { return round_borrows(log_r, 0) && !defers(log_r); }
-constexpr size_t limb_shmem_bytes(int log_r, int dual = 1) {
-    return (size_t)8 * TILE_WORDS * dual + (size_t)16 * limb_tables_w2(log_r) + (uses_ufac(log_r) ? 8 * UFAC_WORDS : 0);
+constexpr size_t limb_shmem_bytes(int log_r) {
+    return (size_t)8 * TILE_WORDS + (size_t)16 * limb_tables_w2(log_r) + (uses_ufac(log_r) ? 8 * UFAC_WORDS : 0);
 }
 
-__device__ __forceinline__ u64 limb_mul(u64 a, u64 b) { return P2HOT_LIMB_MULCF == 2 ? gl::mul1cg(a, b) : gl::mul1(a, b); }
-// v[q] *= w[q] for N independent pairs: three-stream gl::mul3 blocks (no wait states, three chains in flight) where the
-// build asks for them, single streams otherwise
+// the passes' general multiplies (coset scale, inter-pass twiddle, borrowed second factor) run the streams of the Poseidon S-boxes
+__device__ __forceinline__ u64 limb_mul(u64 a, u64 b) { return gl::mul1cg(a, b); }
+// v[q] *= w[q] for N independent pairs: three-stream gl::mul3cg blocks (no wait states, three chains in flight), then a pair or a
+// single stream for what is left
 template <int N>
 __device__ __forceinline__ void limb_mul_n(u64 (&v)[N], const u64 (&w)[N]) {
-    if constexpr (LIMB_MUL3) {
-        int q = 0;
+    int q = 0;
 #pragma unroll
-        for (; q + 3 <= N; q += 3) {
-            const u64 a3[3] = {v[q], v[q + 1], v[q + 2]}, b3[3] = {w[q], w[q + 1], w[q + 2]};
-            u64 r3[3];
-            if constexpr (P2HOT_LIMB_MULCF == 2)
-                gl::mul3cg(a3, b3, r3);  // the 14-instruction form with 3 co-issued moves (what the Poseidon S-boxes run)
-            else if constexpr (P2HOT_LIMB_MULCF != 0)
-                gl::mul3cf(a3, b3, r3);  // carry-free streams (gl_mul3.hpp, round 6): moves ride the multiply-adds, carry adds do not
-            else
-                gl::mul3(a3, b3, r3);
-            v[q] = r3[0], v[q + 1] = r3[1], v[q + 2] = r3[2];
-        }
-        if (N - q == 2) {
-            const u64 a2[2] = {v[q], v[q + 1]}, b2[2] = {w[q], w[q + 1]};
-            u64 r2[2];
-            gl::mul2(a2, b2, r2);
-            v[q] = r2[0], v[q + 1] = r2[1];
-        } else if (N - q == 1) {
-            v[q] = limb_mul(v[q], w[q]);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < N; ++q) v[q] = limb_mul(v[q], w[q]);
+    for (; q + 3 <= N; q += 3) {
+        const u64 a3[3] = {v[q], v[q + 1], v[q + 2]}, b3[3] = {w[q], w[q + 1], w[q + 2]};
+        u64 r3[3];
+        gl::mul3cg(a3, b3, r3);
+        v[q] = r3[0], v[q + 1] = r3[1], v[q + 2] = r3[2];
+    }
+    if (N - q == 2) {
+        const u64 a2[2] = {v[q], v[q + 1]}, b2[2] = {w[q], w[q + 1]};
+        u64 r2[2];
+        gl::mul2(a2, b2, r2);
+        v[q] = r2[0], v[q + 1] = r2[1];
+    } else if (N - q == 1) {
+        v[q] = limb_mul(v[q], w[q]);
     }
 }
 // A wave-uniform constant the optimiser must not see through.  The bias limb O3 is the ONLY contribution to some limbs of a
@@ -391,17 +288,6 @@ __device__ __forceinline__ unsigned wave_uniform(unsigned v) {
 #endif
 }
 
-// P2HOT_LIMB_PHASE: a workgroup barrier the instruction scheduler does not move arithmetic across
-__device__ __forceinline__ void phase_sync() {
-#ifdef P2HOT_EMU
-    __syncthreads();
-#else
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
-
 // the workgroup barrier, or -- after a round whose sub-blocks a wave owns entirely -- nothing but program order
 // (the LDS executes one wave's accesses in order; the emulator's lanes are fibers, so there it stays a barrier)
 template <bool WAVE_PRIVATE>
@@ -409,14 +295,12 @@ __device__ __forceinline__ void round_sync() {
 #ifdef P2HOT_EMU
     __syncthreads();
 #else
-    if constexpr (WAVE_PRIVATE && !LIMB_PHASE) {
+    if constexpr (WAVE_PRIVATE) {
         // the wave barrier alone is declared IntrNoMem: the wavefront-scope fences are what formally order this lane's LDS
         // stores before the other lanes' LDS loads (no instruction is emitted for them; the LDS runs a wave's accesses in order)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else if constexpr (LIMB_PHASE) {
-        phase_sync();
     } else {
         __syncthreads();
     }
@@ -435,7 +319,7 @@ __device__ __forceinline__ void load_inputs(const u64 *gin, unsigned log_stride,
     constexpr unsigned C = 1u << LOG_C;
     constexpr int UPT = 8 >> P;
     constexpr unsigned UW = 512u >> P;
-    const unsigned wave = (threadIdx.x >> 6) & 7u, lane = threadIdx.x & 63;  // (the tile's eight waves; a DUAL workgroup has two tiles)
+    const unsigned wave = (threadIdx.x >> 6) & 7u, lane = threadIdx.x & 63;  // (the tile's eight waves)
 #pragma unroll
     for (int uu = 0; uu < UPT; ++uu) {
         const unsigned u = wave * UW + lane + 64u * (unsigned)uu;
@@ -488,7 +372,7 @@ __device__ __forceinline__ void load_inputs_bitrev(const u64 *src, unsigned tau,
         const unsigned eb = (lo << LOG_C) + c, seb = swz(eb);
 #pragma unroll
         for (int q = 0; q < (1 << P); ++q) {
-            const u64 v = tile[tix(seb, eb, (unsigned)q << (S_LOG + LOG_C))];
+            const u64 v = tile[tix(seb, (unsigned)q << (S_LOG + LOG_C))];
             raw[(uu << P) + q] = v;
             if (nat) nat[((size_t)(lo + ((unsigned)q << S_LOG)) << 12) + ((size_t)tau << LOG_C) + c] = gl::canon(v);
         }
@@ -515,21 +399,21 @@ __device__ __forceinline__ void limb_round(const LimbPassArgs &ra, u64 *tile, co
     constexpr unsigned UW = 512u >> P;               // units per wave: a wave's units cover 512 consecutive tile elements
     [[maybe_unused]] constexpr int UNROLL = FIRST ? UPT : 1;  // `raw` is indexed by uu: registers only when unrolled
     const ntt::PassArgs &a = ra.a;
-    const unsigned wave = (threadIdx.x >> 6) & 7u, lane = threadIdx.x & 63;
+    const unsigned wave = (threadIdx.x >> 6) & 7u, lane = threadIdx.x & 63;  // (the tile's eight waves)
 #pragma unroll UNROLL
     for (int uu = 0; uu < UPT; ++uu) {
         const unsigned u = wave * UW + lane + 64u * (unsigned)uu;
         const unsigned c = u & (C - 1), rest = u >> LOG_C;
         const unsigned lo = rest & ((1u << S_LOG) - 1), hi = rest >> S_LOG;
         const unsigned i0 = (hi << LOG_RB) + lo;
-        const unsigned eb = (i0 << LOG_C) + c, seb = swz(eb);  // the unit's element q is tile word tix(seb, eb, q << (S_LOG + LOG_C))
+        const unsigned eb = (i0 << LOG_C) + c, seb = swz(eb);  // the unit's element q is tile word tix(seb, q << (S_LOG + LOG_C))
         u64 v[1 << P];
         if constexpr (FIRST) {
 #pragma unroll
             for (int q = 0; q < (1 << P); ++q) v[q] = raw[(uu << P) + q];
         } else {
 #pragma unroll
-            for (int q = 0; q < (1 << P); ++q) v[q] = tile[tix(seb, eb, (unsigned)q << (S_LOG + LOG_C))];
+            for (int q = 0; q < (1 << P); ++q) v[q] = tile[tix(seb, (unsigned)q << (S_LOG + LOG_C))];
         }
         if constexpr (FIRST && SCALE == ntt::SCALE_CONST) {
 #pragma unroll
@@ -556,26 +440,8 @@ __device__ __forceinline__ void limb_round(const LimbPassArgs &ra, u64 *tile, co
         x[0].l[2] += O2;
         x[0].l[3] += opaque_u32(O3);
         dft_limbs<P, INV>(x);
-        if constexpr (LIMB_PHASE) phase_sync();  // butterflies (plain adds) | conversions (multiply-adds): every wave switches together
         if constexpr (S_LOG > 0) {
-            if constexpr (LIMB_FOLD3 && !(BORROW && !defers(LOG_R))) {
-                // all 2^P accumulator pairs of the unit, folded three rows per stream
-                constexpr int P0 = round_bits(LOG_R, 0);
-                [[maybe_unused]] const unsigned k0 = ABSORB ? (unsigned)(__brev(hi >> (LOG_R - P0 - LOG_RB)) >> (32 - P0)) : 0u;
-                const W2 *tw = ABSORB ? ltw + T_OFF + ((k0 << (P + 1)) << T_LOG) + lo : ltw + T_OFF + (BORROW ? lo >> P : lo);
-                u64 y[1 << P];
-                fold_groups<(1 << P)>(
-                    [&](int q) {
-                        if (!ABSORB && q == 0) return conv_unit_acc(x[0]);
-                        const unsigned k = q ? (unsigned)(__brev((unsigned)q) >> (32 - P)) : 0u;
-                        const unsigned e = ABSORB ? k * 2 : (k - 1) * 2;
-                        const W2 wa = tw[e << T_LOG], wb = tw[(e + 1) << T_LOG];
-                        return convmul_acc(x[q], wa.a, wa.b, wb.a, wb.b);
-                    },
-                    y);
-#pragma unroll
-                for (int q = 0; q < (1 << P); ++q) tile[tix(seb, eb, (unsigned)q << (S_LOG + LOG_C))] = y[q];
-            } else if constexpr (ABSORB) {
+            if constexpr (ABSORB) {
                 // this round's twiddle times the factor round 0 deferred: slab k0 = the frequency whose first-round block
                 // this unit lies in (position bits LOG_R-P0 .. LOG_R-1, bit-reversed), every output converts through the table
                 constexpr int P0 = round_bits(LOG_R, 0);
@@ -585,9 +451,11 @@ __device__ __forceinline__ void limb_round(const LimbPassArgs &ra, u64 *tile, co
                 for (int q = 0; q < (1 << P); ++q) {
                     const unsigned k = q ? (unsigned)(__brev((unsigned)q) >> (32 - P)) : 0u;
                     const W2 wa = tw[(k * 2) << T_LOG], wb = tw[(k * 2 + 1) << T_LOG];
-                    tile[tix(seb, eb, (unsigned)q << (S_LOG + LOG_C))] = convmul(x[q], wa.a, wa.b, wb.a, wb.b);
+                    tile[tix(seb, (unsigned)q << (S_LOG + LOG_C))] = convmul(x[q], wa.a, wa.b, wb.a, wb.b);
                 }
             } else {
+                // a borrowed table that no later round absorbs (2^10 and 2^11 rows): the small factor is a second multiply here
+                constexpr bool SECOND = BORROW && !defers(LOG_R);
                 const W2 *tw = ltw + T_OFF + (BORROW ? lo >> P : lo);
                 [[maybe_unused]] const u64 *uf = lu + (lo & ((1u << P) - 1)) * 8;
                 tile[seb] = conv_unit(x[0]);
@@ -596,18 +464,17 @@ __device__ __forceinline__ void limb_round(const LimbPassArgs &ra, u64 *tile, co
                 for (int q = 1; q < (1 << P); ++q) {
                     const unsigned k = (unsigned)(__brev((unsigned)q) >> (32 - P));
                     const W2 wa = tw[((k - 1) * 2) << T_LOG], wb = tw[((k - 1) * 2 + 1) << T_LOG];
-                    u64 y = convmul(x[q], wa.a, wa.b, wb.a, wb.b);
-                    if constexpr (BORROW && !defers(LOG_R) && !LIMB_MUL3) y = limb_mul(y, uf[k]);  // (deferred: absorbed by a later round's table)
-                    if constexpr (BORROW && !defers(LOG_R) && LIMB_MUL3) {
+                    const u64 y = convmul(x[q], wa.a, wa.b, wb.a, wb.b);
+                    if constexpr (SECOND) {
                         yb[q - 1] = y, ub[q - 1] = uf[k];
                     } else {
-                        tile[tix(seb, eb, (unsigned)q << (S_LOG + LOG_C))] = y;
+                        tile[tix(seb, (unsigned)q << (S_LOG + LOG_C))] = y;
                     }
                 }
-                if constexpr (BORROW && !defers(LOG_R) && LIMB_MUL3) {  // the second factors of the unit's outputs, three streams at a time
+                if constexpr (SECOND) {  // the second factors of the unit's outputs, three streams at a time
                     limb_mul_n<(1 << P) - 1>(yb, ub);
 #pragma unroll
-                    for (int q = 1; q < (1 << P); ++q) tile[tix(seb, eb, (unsigned)q << (S_LOG + LOG_C))] = yb[q - 1];
+                    for (int q = 1; q < (1 << P); ++q) tile[tix(seb, (unsigned)q << (S_LOG + LOG_C))] = yb[q - 1];
                 }
             }
         } else {
@@ -622,57 +489,27 @@ __device__ __forceinline__ void limb_round(const LimbPassArgs &ra, u64 *tile, co
                 const W2 *sb = ra.sbase + (((z << (log_stride - LOG_C)) + (base0 >> LOG_C)) << 1);
                 w0 = sb[0].a, w1 = sb[0].b, w2 = sb[1].a, w3 = sb[1].b;
             }
-            auto conv_last = [&](const L4 &v_) { return LAST == LAST_UNIT ? conv_unit(v_) : convmul(v_, w0, w1, w2, w3); };
-            auto conv_last_all = [&](u64 (&y_)[1 << P]) {  // y_[q] = conv_last(x[q])
-                if constexpr (LIMB_FOLD3) {
-                    fold_groups<(1 << P)>(
-                        [&](int q) { return LAST == LAST_UNIT ? conv_unit_acc(x[q]) : convmul_acc(x[q], w0, w1, w2, w3); }, y_);
-                } else {
+            auto conv_last_all = [&](u64 (&y_)[1 << P]) {
 #pragma unroll
-                    for (int q = 0; q < (1 << P); ++q) y_[q] = conv_last(x[q]);
-                }
+                for (int q = 0; q < (1 << P); ++q) y_[q] = LAST == LAST_UNIT ? conv_unit(x[q]) : convmul(x[q], w0, w1, w2, w3);
             };
             if constexpr (LOG_C > 0 && P <= 2) {  // (a radix-8 last round keeps too much alive: it goes through LDS like the contiguous pass)
                 const u32 off0 = ((i0 << log_stride) + c) * 8u;  // bytes; the row steps q << log_stride are wave-uniform
                 const char *tw = reinterpret_cast<const char *>(ra.twid + base0);
                 char *go = reinterpret_cast<char *>(gout);
-                if constexpr (LIMB_MUL3) {
-                    u64 y[1 << P], t[1 << P];
+                u64 y[1 << P], t[1 << P];
 #pragma unroll
-                    for (int q = 0; q < (1 << P); ++q) t[q] = *reinterpret_cast<const u64 *>(tw + ((size_t)q << log_stride) * 8 + off0);
-                    conv_last_all(y);
-                    limb_mul_n<(1 << P)>(y, t);
+                for (int q = 0; q < (1 << P); ++q) t[q] = *reinterpret_cast<const u64 *>(tw + ((size_t)q << log_stride) * 8 + off0);
+                conv_last_all(y);
+                limb_mul_n<(1 << P)>(y, t);
 #pragma unroll
-                    for (int q = 0; q < (1 << P); ++q)
-                        *reinterpret_cast<u64 *>(go + ((size_t)q << log_stride) * 8 + off0) = y[q];  // (a strided pass is never the last: no canon)
-                } else {
-#pragma unroll
-                    for (int q = 0; q < (1 << P); ++q) {
-                        const size_t step = ((size_t)q << log_stride) * 8;
-                        const u64 v_ = limb_mul(conv_last(x[q]), *reinterpret_cast<const u64 *>(tw + step + off0));
-                        *reinterpret_cast<u64 *>(go + step + off0) = v_;
-#ifndef P2HOT_EMU
-                        if ((q & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // four outputs at a time: the twiddle loads are not hoisted past this
-#endif
-                    }
-                }
-            } else if constexpr (P == 3 && LIMB_DIRECT_CONTIG) {
-                // the contiguous pass: a unit's eight outputs are 64 consecutive bytes of the block -- four 16-byte stores
-                // (measured slower than the LDS round trip: 5.01 vs 4.87 ms for the LDE's pass; off by default)
-                W2 *go = reinterpret_cast<W2 *>(gout + i0);
-#pragma unroll
-                for (int q = 0; q < 8; q += 2) {
-                    W2 pr;
-                    pr.a = conv_last(x[q]);
-                    pr.b = conv_last(x[q + 1]);
-                    if (a.canon_out) pr.a = gl::canon(pr.a), pr.b = gl::canon(pr.b);
-                    go[q >> 1] = pr;
-                }
+                for (int q = 0; q < (1 << P); ++q)
+                    *reinterpret_cast<u64 *>(go + ((size_t)q << log_stride) * 8 + off0) = y[q];  // (a strided pass is never the last: no canon)
             } else {
                 u64 y[1 << P];
                 conv_last_all(y);
 #pragma unroll
-                for (int q = 0; q < (1 << P); ++q) tile[tix(seb, eb, (unsigned)q << LOG_C)] = y[q];
+                for (int q = 0; q < (1 << P); ++q) tile[tix(seb, (unsigned)q << LOG_C)] = y[q];
             }
         }
     }
@@ -680,37 +517,31 @@ __device__ __forceinline__ void limb_round(const LimbPassArgs &ra, u64 *tile, co
     if constexpr (RI + 1 < n_rounds(LOG_R)) {
         round_sync<(LOG_RB + LOG_C <= 9)>();
         limb_round<INV, LOG_R, LOG_C, SCALE, LAST, RI + 1>(ra, tile, ltw, lu, raw, next_gin, gout, log_stride, z, base0);
-    } else if constexpr (LOG_C == 0 ? !(P == 3 && LIMB_DIRECT_CONTIG) : P == 3) {
+    } else if constexpr (LOG_C == 0 || P == 3) {
         round_sync<(LOG_RB + LOG_C <= 9)>();  // the store phase reads what this round wrote
     }
 }
 
 // One pass over 2^LOG_R x 2^LOG_C tiles (LOG_R + LOG_C = 12); LOG_C = 0 is the contiguous (last) pass.
-// grid = (tiles per polynomial >> tiles_log >> (DUAL - 1), polynomials, z), 512 * DUAL threads, limb_shmem_bytes(LOG_R, DUAL) of
-// dynamic LDS.  DUAL = 2: threads 512..1023 transform the NEXT tile group side by side with threads 0..511 (their own tile in LDS,
-// the round tables shared): one workgroup then holds all four waves of every SIMD, so a workgroup barrier is a SIMD-wide one.
+// grid = (tiles per polynomial >> tiles_log, polynomials, z), 512 threads, limb_shmem_bytes(LOG_R) of dynamic LDS.
 // Workgroup barriers: one after the first round and one per tile; the later rounds and the store phase are wave-private.
-template <bool INV, int LOG_R, int LOG_C, int SCALE, int LAST = LAST_UNIT, int DUAL = 1, bool BRIN = false>
-__global__ void __launch_bounds__(NT * DUAL, LIMB_MIN_WAVES) ntt_limbpass_kernel(LimbPassArgs ra) {
+template <bool INV, int LOG_R, int LOG_C, int SCALE, int LAST = LAST_UNIT, bool BRIN = false>
+__global__ void __launch_bounds__(NT, LIMB_MIN_WAVES) ntt_limbpass_kernel(LimbPassArgs ra) {
     static_assert(LOG_R + LOG_C == TILE_LOG, "a tile is 4096 elements");
-    static_assert(DUAL == 1 || DUAL == 2, "one or two tiles side by side");
-    static_assert(!BRIN || (LOG_C > 0 && DUAL == 1 && !INV), "the bit-reversed source is the first pass of a two-pass coset LDE");
-    P2HOT_DYN_SHARED(u64, tile_all);
+    static_assert(!BRIN || (LOG_C > 0 && !INV), "the bit-reversed source is the first pass of a two-pass coset LDE");
+    P2HOT_DYN_SHARED(u64, tile);
     const ntt::PassArgs &a = ra.a;
-    const unsigned tid = threadIdx.x & (NT - 1);                          // the thread's place among its tile's 512
-    const unsigned half = DUAL == 2 ? wave_uniform(threadIdx.x >> 9) : 0u;  // which of the workgroup's tiles
-    u64 *tile = tile_all + (size_t)half * TILE_WORDS;
-    W2 *ltw = reinterpret_cast<W2 *>(tile_all + (size_t)DUAL * TILE_WORDS);
+    const unsigned tid = threadIdx.x & (NT - 1);  // (= threadIdx.x; the mask hands the optimiser the bound)
+    W2 *ltw = reinterpret_cast<W2 *>(tile + TILE_WORDS);
     u64 *lu = reinterpret_cast<u64 *>(ltw + limb_tables_w2(LOG_R));
-    for (unsigned e = threadIdx.x; e < (unsigned)limb_tables_w2(LOG_R); e += NT * DUAL) ltw[e] = ra.tw_all[e];
+    for (unsigned e = threadIdx.x; e < (unsigned)limb_tables_w2(LOG_R); e += NT) ltw[e] = ra.tw_all[e];
     if constexpr (uses_ufac(LOG_R))
         if (threadIdx.x < (unsigned)UFAC_WORDS) lu[threadIdx.x] = ra.ufac[threadIdx.x];
     __syncthreads();
     const unsigned log_stride = LOG_C ? a.log_nblk - LOG_R : 0u;  // the contiguous pass is the last one: blocks of one tile
     const unsigned tiles_per_blk_log = log_stride - LOG_C;
-    // (xcd_remap counts WORKGROUPS: the host passes log2 of gridDim.x; a DUAL workgroup takes two consecutive tile groups)
-    const size_t wg0 = (LOG_C && ra.xcd_remap) ? (((size_t)(blockIdx.x & 7u) << (ra.xcd_remap - 3)) | (blockIdx.x >> 3)) : blockIdx.x;
-    const size_t wg = wg0 * DUAL + half;
+    // (xcd_remap counts WORKGROUPS: the host passes log2 of gridDim.x)
+    const size_t wg = (LOG_C && ra.xcd_remap) ? (((size_t)(blockIdx.x & 7u) << (ra.xcd_remap - 3)) | (blockIdx.x >> 3)) : blockIdx.x;
     const size_t z_begin = ra.zloop ? 0 : blockIdx.z, z_end = ra.zloop ? ra.zloop : blockIdx.z + 1;
     const bool same_input = a.in_z_stride == 0;  // every z slice transforms the same polynomials (coset LDE): fetch them once
     const unsigned e0 = (tid >> 6) * 512u + (tid & 63u);  // store phase: wave w moves tile elements [512 w, 512 w + 512)
@@ -747,17 +578,17 @@ __global__ void __launch_bounds__(NT * DUAL, LIMB_MIN_WAVES) ntt_limbpass_kernel
             }
             limb_round<INV, LOG_R, LOG_C, SCALE, LAST, 0>(ra, tile, ltw, lu, raw, next, out, log_stride, z, base0);
             constexpr int LAST_P = round_bits(LOG_R, n_rounds(LOG_R) - 1);
-            if constexpr (LOG_C == 0 && !(LAST_P == 3 && LIMB_DIRECT_CONTIG)) {
+            if constexpr (LOG_C == 0) {
                 // canonical representatives or not is the launch's choice: ONE wave-uniform branch around the eight stores
                 // (as `canon_out ? canon(v) : v` it was a 64-bit compare, an add and four selects per word; the empty asm keeps
                 // the optimiser from merging the two arms back into selects)
                 if (a.canon_out) {
                     opaque_branch();
 #pragma unroll
-                    for (unsigned j = 0; j < 8; ++j) out[e0 + 64 * j] = gl::canon(tile[tix(se0, e0, 64 * j)]);
+                    for (unsigned j = 0; j < 8; ++j) out[e0 + 64 * j] = gl::canon(tile[tix(se0, 64 * j)]);
                 } else {
 #pragma unroll
-                    for (unsigned j = 0; j < 8; ++j) out[e0 + 64 * j] = tile[tix(se0, e0, 64 * j)];
+                    for (unsigned j = 0; j < 8; ++j) out[e0 + 64 * j] = tile[tix(se0, 64 * j)];
                 }
             } else if constexpr (LOG_C > 0 && LAST_P == 3) {
                 // a strided pass whose last round is radix 8 (2^9 and 2^6 rows): inter-pass twiddle + store from LDS.
@@ -766,31 +597,20 @@ __global__ void __launch_bounds__(NT * DUAL, LIMB_MIN_WAVES) ntt_limbpass_kernel
                 const unsigned lane = tid & 63u;
                 const u32 off0 = (((lane >> LOG_C) << log_stride) + (lane & (C - 1))) * 8u;  // bytes, per lane
                 const unsigned U0 = wave_uniform(tid >> 6) * 512u;
-                if constexpr (LIMB_MUL3) {  // the thread's eight products as three-stream blocks
-                    u64 v8[8], w8[8];
+                u64 v8[8], w8[8];  // the thread's eight products as three-stream blocks
 #pragma unroll
-                    for (unsigned j = 0; j < 8; ++j) {
-                        const unsigned U = U0 + 64 * j;
-                        const size_t step = ((size_t)(U >> LOG_C) << log_stride) + (U & (C - 1));
-                        w8[j] = *reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(ra.twid + base0 + step) + off0);
-                        v8[j] = tile[tix(se0, e0, 64 * j)];
-                    }
-                    limb_mul_n<8>(v8, w8);
+                for (unsigned j = 0; j < 8; ++j) {
+                    const unsigned U = U0 + 64 * j;
+                    const size_t step = ((size_t)(U >> LOG_C) << log_stride) + (U & (C - 1));
+                    w8[j] = *reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(ra.twid + base0 + step) + off0);
+                    v8[j] = tile[tix(se0, 64 * j)];
+                }
+                limb_mul_n<8>(v8, w8);
 #pragma unroll
-                    for (unsigned j = 0; j < 8; ++j) {
-                        const unsigned U = U0 + 64 * j;
-                        const size_t step = ((size_t)(U >> LOG_C) << log_stride) + (U & (C - 1));
-                        *reinterpret_cast<u64 *>(reinterpret_cast<char *>(out + step) + off0) = v8[j];
-                    }
-                } else {
-#pragma unroll 2
-                    for (unsigned j = 0; j < 8; ++j) {
-                        const unsigned U = U0 + 64 * j;
-                        const size_t step = ((size_t)(U >> LOG_C) << log_stride) + (U & (C - 1));
-                        const u64 w = *reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(ra.twid + base0 + step) + off0);
-                        u64 v = limb_mul(tile[tix(se0, e0, 64 * j)], w);
-                        *reinterpret_cast<u64 *>(reinterpret_cast<char *>(out + step) + off0) = v;
-                    }
+                for (unsigned j = 0; j < 8; ++j) {
+                    const unsigned U = U0 + 64 * j;
+                    const size_t step = ((size_t)(U >> LOG_C) << log_stride) + (U & (C - 1));
+                    *reinterpret_cast<u64 *>(reinterpret_cast<char *>(out + step) + off0) = v8[j];
                 }
             }
             __syncthreads();  // the next tile's first round overwrites what other waves may still be reading

@@ -47,27 +47,6 @@ __device__ __forceinline__ u64 sbox7(u64 x) {  // poseidon.rs:690-696
     return gl::mul(x3, x4);
 }
 
-// P2HOT_SBOX_CF (default 2): the S-box products through the carry-free multiply streams of round 6 -- 2: gl::mul3cg / mul1cg (two
-// partial products chained through the multiply-add's addend, the one real carry left to the multiply-add's own carry-out: 14
-// instructions, 3 of them co-issued moves); 1: gl::mul3cf / mul1cf (all three chained: 16 instructions, 4 moves); 0: the round-3
-// streams (gl::mul3 / mul1: 14 instructions, 3 carry adds)
-#ifndef P2HOT_SBOX_CF
-#define P2HOT_SBOX_CF 2
-#endif
-__device__ __forceinline__ u64 sbox_mul1(u64 a, u64 b) {
-    return P2HOT_SBOX_CF >= 2 ? gl::mul1cg(a, b) : P2HOT_SBOX_CF ? gl::mul1cf(a, b) : gl::mul1(a, b);
-}
-__device__ __forceinline__ void sbox_mul3(const u64 a[3], const u64 b[3], u64 r[3]) {
-    if (P2HOT_SBOX_CF == 3)
-        gl::mul3ch(a, b, r);
-    else if (P2HOT_SBOX_CF == 2)
-        gl::mul3cg(a, b, r);
-    else if (P2HOT_SBOX_CF)
-        gl::mul3cf(a, b, r);
-    else
-        gl::mul3(a, b, r);
-}
-
 // a + c for a round constant c (canonical): the 64-bit add, its wrap as a compare, and the fold-back of 2^64 = 2^32 - 1 as ONE multiply-add
 // on the select (hipcc's form of gl::add_canon is a second 64-bit add and two selects: 5 instructions instead of 4)
 __device__ __forceinline__ u64 ark(u64 a, u64 c) {
@@ -91,21 +70,23 @@ __device__ __forceinline__ u32 opaque_zero() {
 #endif
 }
 
+// The S-box products run the carry-free multiply streams gl::mul3cg / mul1cg (gl_mul3.hpp: 14 instructions, 3 of them co-issued
+// moves; the streams measured against them: profiles/r06_sbox_hybrid_ab.txt).
 // x^7 of one word with the hand-scheduled multiply (the partial rounds' single S-box)
 __device__ __forceinline__ u64 sbox7_asm(u64 x) {
-    u64 x2 = sbox_mul1(x, x);
-    u64 x4 = sbox_mul1(x2, x2);
-    u64 x3 = sbox_mul1(x, x2);
-    return sbox_mul1(x3, x4);
+    u64 x2 = gl::mul1cg(x, x);
+    u64 x4 = gl::mul1cg(x2, x2);
+    u64 x3 = gl::mul1cg(x, x2);
+    return gl::mul1cg(x3, x4);
 }
 
 // x^7 of three independent words at once: x2 = x*x; (x3 = x*x2 and x4 = x2*x2 are independent); x7 = x3*x4
 __device__ __forceinline__ void sbox7_x3(u64 &a, u64 &b, u64 &c) {
     u64 x[3] = {a, b, c}, x2[3], x3[3], x4[3];
-    sbox_mul3(x, x, x2);
-    sbox_mul3(x, x2, x3);
-    sbox_mul3(x2, x2, x4);
-    sbox_mul3(x3, x4, x);
+    gl::mul3cg(x, x, x2);
+    gl::mul3cg(x, x2, x3);
+    gl::mul3cg(x2, x2, x4);
+    gl::mul3cg(x3, x4, x);
     a = x[0];
     b = x[1];
     c = x[2];
@@ -411,11 +392,10 @@ __device__ __forceinline__ void partial_rounds4(u64 s[12], u64 c1, u64 c2, u64 c
 // S-boxes instead of three 12-row passes.  The matrix entries are s_mov_b32 literals in the instruction stream (P2_LITERAL_QUAL).  (The
 // plain power M^4 would not fit -- its rows sum to 1.04 * 2^32 -- but the column-0-dropped product (MD)^3 M does: partial_rounds4
 // above runs four rounds a pass; this three-round form is the tail batch.)  The rounds' scalar constants
-// (P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 r]) ride the chains as starting addends: c1, c2 those of this batch's second and third round,
-// cn that of the NEXT pass's first round (fused into row 0); this batch's first is already in s[0].
-// TAIL (the last batch): cv = the constant VECTOR of the full round that follows, fused into all twelve rows (cn unused).
-template <bool TAIL = false>
-__device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, u64 cn, const u64 *cv = nullptr) {
+// (P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 r]) ride the chains as starting addends: c1, c2 those of this batch's second and third round
+// (its first is already in s[0]), and cv = the constant VECTOR of the full round that follows, fused into all twelve rows (eleven
+// 4-instruction additions less per permutation than adding it afterwards: -0.3 % cycles, profiles/r06_partial_rounds_ab.txt).
+__device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, const u64 *cv) {
     u32 xl[12], xh[12];
     const u64 z0 = sbox7_asm(s[0]);  // round 0's scalar is already in s[0]: the previous pass fused it into its row 0
     xl[0] = (u32)z0;
@@ -448,7 +428,7 @@ __device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, u64 c
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int i = g + t;
-            const u64 ci = TAIL ? cv[i] : (i == 0 ? cn : 0);
+            const u64 ci = cv[i];
             bl[t] = (u64)s1l * MDM.v[12 * i] + (u64)s2l * MDS1.v[12 * i] + (u32)ci;
             bh[t] = (u64)s1h * MDM.v[12 * i] + (u64)s2h * MDS1.v[12 * i] + (ci >> 32);
 #pragma unroll
@@ -464,11 +444,6 @@ __device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, u64 c
     }
 }
 
-#ifndef P2HOT_TAIL_BATCH
-#define P2HOT_TAIL_BATCH 1  // 1: the last batch of partial rounds is its own copy with round 26's constant vector fused into its rows (eleven
-                            // 4-instruction additions less per permutation: -0.3 % cycles, profiles/r06_partial_rounds_ab.txt); 0: the vector is
-                            // added after the last batch
-#endif
 // the permutation; output words are NOT canonicalised (callers canonicalise what they emit).
 // Round r: ARK(r) was already added by the previous MDS (or up front for r = 0); S-box; MDS + ARK(r+1).
 // `out_groups`: which output word triples the caller reads (bit g = words 3g..3g+2), `out_single`: one more word (3 or 8) it reads;
@@ -500,15 +475,8 @@ __device__ inline void permute(u64 s[12], unsigned out_groups = 0xFu, int out_si
         partial_rounds4(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 1)], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 2)],
                         P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 3)], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * (round + 4)]);
     const u32 z26 = opaque_zero();
-    if (P2HOT_TAIL_BATCH) {
-        partial_rounds3<true>(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 24], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 25], 0,
-                              P2_POSEIDON_PUSHED_ROUND_CONSTANTS + 12 * 26 + z26);
-    } else {
-        partial_rounds3(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 24], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 25],
-                        P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 26]);
-#pragma unroll
-        for (int i = 1; i < 12; ++i) s[i] = ark(s[i], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 26 + i + z26]);
-    }
+    partial_rounds3(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 24], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 25],
+                    P2_POSEIDON_PUSHED_ROUND_CONSTANTS + 12 * 26 + z26);
     round = 26;
 #pragma unroll 1
     for (int k = 0; k < 3; ++k, ++round) {

@@ -632,7 +632,7 @@ def test_limb_bias_represents_zero():
 def test_limb_unit_limbs_stay_in_range(p, inv):
     """every output limb of a 2^p-point unit stays in [0, 2^29) over all split inputs (exact linear-form bounds, checked on the
     extreme vertices themselves and -- for p = 1, 2 -- on every vertex of the input box), so the conversions' accumulators stay
-    below 2^63 (nttl.hpp:192 convmul_acc, conv_unit_acc)"""
+    below 2^63 (nttl.hpp convmul, conv_unit)"""
     bounds = unit_bounds(p, inv)
     lmax = [0] * 4
     for q, i, lo, hi, v_lo, v_hi in bounds:
@@ -649,10 +649,10 @@ def test_limb_unit_limbs_stay_in_range(p, inv):
                 v[4 * q + i] = SPLIT_MAX[i] * s
             out = unit(words_of(v), p, inv)
             assert all(0 <= l < 2**29 for limbs in out for l in limbs), signs
-    # convmul_acc: al = sum L_i * lo32(W_i), ah = sum L_i * hi32(W_i), halves of any 64-bit table word
+    # convmul: al = sum L_i * lo32(W_i), ah = sum L_i * hi32(W_i), halves of any 64-bit table word
     acc = sum(lmax[i] * (2**32 - 1) for i in range(4))
     assert acc < 2**63, acc
-    # conv_unit_acc: al = L3 * lo32(B3) + L0 + (L1 << 24), ah = L3 * hi32(B3) + (L2 << 16), and al + ah 2^32 = sum L_i B^i (mod P)
+    # conv_unit: al = L3 * lo32(B3) + L0 + (L1 << 24), ah = L3 * hi32(B3) + (L2 << 16), and al + ah 2^32 = sum L_i B^i (mod P)
     b3 = K["B3"]
     al = lmax[3] * (b3 & 0xFFFFFFFF) + lmax[0] + (lmax[1] << 24)
     ah = lmax[3] * (b3 >> 32) + (lmax[2] << 16)
