@@ -89,7 +89,7 @@ struct p2hot_ctx {
     } scratch[4];  // 0: NTT temporary, 1: final_poly, 2: FRI commit phase, 3: all-gather staging of the sharded commit (grow-only, reused across calls)
     // coset scale tables keyed by (log_n, rate_bits, shift, first block, block count, first-pass log_r)
     std::map<std::tuple<unsigned, unsigned, u64, size_t, size_t, unsigned>, u64 *> scale_cache;
-    std::map<std::tuple<int, unsigned, unsigned>, u64 *> twid_cache;
+    std::map<std::tuple<int, unsigned, unsigned>, u64 *> twid_cache;  // (inverse, log_nblk, log_r) -> inter-pass twiddle table
     // grow-only cache of device blocks for the host-pointer entry points: a fresh hipMalloc of the 9 GB LDE matrix
     // costs up to a second (the driver clears VRAM), so blocks go back to this list instead of hipFree
     std::vector<p2hot_ctx *> helpers;   // p2hot_prove_openings_many: sibling contexts on the same GPU, each with its own stream
@@ -97,7 +97,7 @@ struct p2hot_ctx {
     std::vector<struct p2hot_challenger *> helper_challengers;
     std::mutex pool_mu;  // pool_free / pool_live / scratch bookkeeping: frees may come from another thread (a Drop, a GC finaliser)
     std::vector<std::pair<void *, size_t>> pool_free;  // (pointer, capacity)
-    std::map<void *, size_t> pool_live;  // (inverse, log_nblk, log_r) -> inter-pass twiddle table
+    std::map<void *, size_t> pool_live;
     // the same for PINNED host blocks handed to the caller (p2hot_host_alloc): the flat leaf matrix behind MerkleTree::get
     std::vector<std::pair<void *, size_t>> host_pool_free;
     std::map<void *, size_t> host_pool_live;
@@ -626,8 +626,19 @@ extern "C" const char *p2hot_profile_json(p2hot_ctx *ctx, int reset) {
 }
 
 // ------------------------------------------------------------------ NTT pass planning
+enum PassKernel { PASS_LDS, PASS_WORD, PASS_LIMB };  // ntt::ntt_pass_kernel (radix 2 in LDS), ntt::ntt_regpass_kernel, nttl::ntt_limbpass_kernel
 struct Pass {
-    unsigned log_r, log_c;
+    unsigned log_r, log_c;  // the tile: 2^log_r rows (the bits this pass transforms) x 2^log_c columns
+    unsigned log_nblk;      // the blocks this pass works in: log_n less the bits of the passes before it
+    PassKernel kernel;
+    bool table_twid;        // the inter-pass twiddles come from a table (ntt::RegPassArgs::twid), not from the root tables
+};
+struct NttPlan {
+    std::vector<Pass> passes;
+    bool limb_all;          // every pass is a limb pass: an inverse's 1/n moves from the first pass (SCALE_CONST) to the last (LAST_CONST)
+    bool first_limb_shape;  // the first pass is strided on a limb tile: the coset scale tables include the tile-shaped ones --
+                            // by shape, whether or not the limb kernels are switched on (scale_cache outlives p2hot_tune_ntt)
+    bool lde_reads_bitrev;  // a coset LDE may read its coefficients bit-reversed (nttl.hpp BRIN): two limb passes, the first strided
 };
 
 static std::vector<Pass> plan_passes(unsigned log_n, unsigned maxb) {
@@ -655,6 +666,33 @@ static std::vector<Pass> plan_passes(unsigned log_n, unsigned maxb) {
     return p;
 }
 
+static bool limb_supported(unsigned log_r, unsigned log_c) {
+    if (log_r + log_c != (unsigned)nttl::TILE_LOG) return false;
+    return log_r == 12 || (log_r >= 4 && log_r <= 10);
+}
+
+// Which kernel every pass of a 2^log_n transform runs, from the size and the context's knobs alone (no device state): what
+// run_dif launches, what coset_scale_tables builds and whether commit_dev_impl skips its bit reversal are all read from here.
+static NttPlan plan_ntt(const p2hot_ctx *ctx, unsigned log_n) {
+    NttPlan plan{plan_passes(log_n, ctx->ntt_strided_bits), true, false, false};
+    const bool limb_on = ctx->use_limb && ctx->use_regpass && ctx->ntt_radix_bits == 3;
+    unsigned log_nblk = log_n;
+    for (Pass &ps : plan.passes) {
+        ps.log_nblk = log_nblk;
+        // strided passes multiply by w_{n'}^(col * k1) on the way out: the same 2^log_nblk values for every block, polynomial
+        // and coset, kept as a table (<= 128 MiB) laid out like a block so that the load is as coalesced as the store
+        ps.table_twid = log_nblk > ps.log_r && log_nblk <= 24;
+        // a strided limb pass has no other source of inter-pass twiddles than the table
+        const bool limb = limb_on && limb_supported(ps.log_r, ps.log_c) && (ps.log_c == 0 || ps.table_twid);
+        ps.kernel = limb ? PASS_LIMB : ctx->use_regpass ? PASS_WORD : PASS_LDS;
+        plan.limb_all = plan.limb_all && limb;
+        log_nblk -= ps.log_r;
+    }
+    const Pass &first = plan.passes[0];
+    plan.first_limb_shape = first.log_c > 0 && limb_supported(first.log_r, first.log_c);
+    plan.lde_reads_bitrev = ctx->lde_reads_bitrev && plan.limb_all && plan.passes.size() == 2;  // (the first of two passes is strided)
+    return plan;
+}
 
 // ------------------------------------------------------------------ limb passes (nttl.hpp)
 // the round tables of a 2^log_r-row tile, concatenated in the layout the kernel copies to LDS (nttl::round_table_off)
@@ -704,39 +742,142 @@ static int lds_opt_in(p2hot_ctx *ctx, const void *kernel, size_t shm) {
     return P2HOT_OK;
 }
 
-static bool limb_supported(unsigned log_r, unsigned log_c) {
-    if (log_r + log_c != (unsigned)nttl::TILE_LOG) return false;
-    return log_r == 12 || (log_r >= 4 && log_r <= 10);
+// the inter-pass twiddle table of a pass that takes one (Pass::table_twid), made on first use; null for every other pass
+static int interpass_twiddles(p2hot_ctx *ctx, bool inverse, const Pass &ps, const u64 **twid) {
+    *twid = nullptr;
+    if (!ps.table_twid) return P2HOT_OK;
+    auto key = std::make_tuple((int)inverse, ps.log_nblk, ps.log_r);
+    auto it = ctx->twid_cache.find(key);
+    if (it == ctx->twid_cache.end()) {
+        u64 *t = nullptr;
+        P2_HIP(ctx, hipMalloc((void **)&t, (size_t)8 << ps.log_nblk));
+        P2HOT_LAUNCH(ntt::interpass_twiddle_kernel, dim3(cdiv((size_t)1 << ps.log_nblk, 256)), dim3(256), 0, ctx->stream, t,
+                     ps.log_nblk, ps.log_r, inverse ? ctx->inv : ctx->fwd);
+        P2_LAUNCH_CHECK(ctx);
+        it = ctx->twid_cache.emplace(key, t).first;
+    }
+    *twid = it->second;
+    return P2HOT_OK;
 }
 
-// launches one limb pass; `last_const` != 1 multiplies every output of this (last) pass by it (the 1/n of the inverse transform)
+// ------------------------------------------------------------------ word passes (ntt.hpp)
+// radix 8 on 512 threads: one kernel per (direction, scale mode, contiguous single-tile transform), the per-point mode tests
+// compiled out; radix 16 on 256 threads: one per direction
+using WordKernel = void (*)(ntt::RegPassArgs);
+template <bool INV, bool CONTIG>
+constexpr WordKernel word_kernel512(int scale_mode) {
+    if (scale_mode == ntt::SCALE_TABLE) return ntt::ntt_regpass_kernel<INV, 512, CONTIG ? 8 : 6, ntt::SCALE_TABLE, CONTIG>;
+    if (scale_mode == ntt::SCALE_CONST) return ntt::ntt_regpass_kernel<INV, 512, CONTIG ? 8 : 6, ntt::SCALE_CONST, CONTIG>;
+    return ntt::ntt_regpass_kernel<INV, 512, CONTIG ? 8 : 6, ntt::SCALE_NONE, CONTIG>;
+}
+template <bool INV>
+constexpr WordKernel word_kernel(unsigned radix_bits, int scale_mode, bool contig) {
+    if (radix_bits != 3) return ntt::ntt_regpass_kernel<INV, 256, 4>;
+    return contig ? word_kernel512<INV, true>(scale_mode) : word_kernel512<INV, false>(scale_mode);
+}
+
+static int launch_word_pass(p2hot_ctx *ctx, const Pass &ps, const ntt::PassArgs &a, bool inverse, dim3 grid, unsigned xcd_remap,
+                            unsigned zloop) {
+    ntt::RegPassArgs ra{};
+    ra.a = a;
+    P2_TRY(interpass_twiddles(ctx, inverse, ps, &ra.twid));
+    ra.local = inverse ? ctx->local_inv : ctx->local_fwd;
+    ra.inverse = inverse;
+    ra.xcd_remap = xcd_remap, ra.zloop = zloop;
+    // rounds of radix <= 2^maxp, remainder split as evenly as possible.  Radix 8 with 512 threads
+    // (8 points per lane, <= 64 VGPRs, 8 waves/SIMD) measured faster than radix 16 with 256 threads:
+    // the pass is mostly VALU issue, and the extra waves cover the global / LDS / barrier waits.
+    const unsigned maxp = ctx->ntt_radix_bits;
+    unsigned rem = ps.log_r, k = 0;
+    const unsigned nr = (rem + maxp - 1) / maxp;
+    for (unsigned q = 0; q < nr; ++q) {
+        unsigned part = (rem + (nr - q) - 1) / (nr - q);
+        ra.rounds[k++] = part;
+        rem -= part;
+    }
+    const size_t shm = (size_t)8 * ntt::TILE_WORDS_PADDED;
+    const bool contig = ps.log_c == 0 && ps.log_nblk == ps.log_r;
+    const WordKernel kernel = inverse ? word_kernel<true>(maxp, a.scale_mode, contig) : word_kernel<false>(maxp, a.scale_mode, contig);
+    P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(kernel), shm));
+    P2HOT_LAUNCH(kernel, grid, dim3(maxp == 3 ? 512 : 256), shm, ctx->stream, ra);
+    return P2HOT_OK;
+}
+
+// ------------------------------------------------------------------ limb passes: kernel choice and launch
+// The instantiation for one tile shape, or null where there is none.  The last conversion multiplies by 1 (LAST_UNIT), by a
+// constant (LAST_CONST: the inverse transform's 1/n -- the contiguous pass without a scale only) or -- the strided first pass of
+// a coset LDE -- by the tile's share of the coset scale (LAST_TILE: SCALE_TABLE only; a contiguous pass asks for LAST_UNIT
+// there).  The bit-reversed source (BRIN) exists for that strided first pass alone: forward, SCALE_TABLE / LAST_TILE, no 12-bit tile.
+using LimbKernel = void (*)(nttl::LimbPassArgs);
+template <bool INV, int LR>
+constexpr LimbKernel limb_kernel(int scale_mode, int last, bool brin) {
+    constexpr int LC = nttl::TILE_LOG - LR;
+    if (brin) {
+        if constexpr (!INV && LR != 12)
+            if (scale_mode == ntt::SCALE_TABLE && last == nttl::LAST_TILE)
+                return nttl::ntt_limbpass_kernel<false, LR, LC, ntt::SCALE_TABLE, nttl::LAST_TILE, true>;
+        return nullptr;
+    }
+    if (last == nttl::LAST_CONST) {
+        if constexpr (LR == 12)
+            if (scale_mode == ntt::SCALE_NONE) return nttl::ntt_limbpass_kernel<INV, 12, 0, ntt::SCALE_NONE, nttl::LAST_CONST>;
+        return nullptr;
+    }
+    if (scale_mode == ntt::SCALE_TABLE) {
+        if (last == nttl::LAST_TILE) return nttl::ntt_limbpass_kernel<INV, LR, LC, ntt::SCALE_TABLE, nttl::LAST_TILE>;
+        return nttl::ntt_limbpass_kernel<INV, LR, LC, ntt::SCALE_TABLE, nttl::LAST_UNIT>;
+    }
+    if (last != nttl::LAST_UNIT) return nullptr;
+    if (scale_mode == ntt::SCALE_CONST) return nttl::ntt_limbpass_kernel<INV, LR, LC, ntt::SCALE_CONST, nttl::LAST_UNIT>;
+    return nttl::ntt_limbpass_kernel<INV, LR, LC, ntt::SCALE_NONE, nttl::LAST_UNIT>;
+}
+template <int... LR>
+constexpr LimbKernel limb_kernel_among(bool inverse, unsigned log_r, int scale_mode, int last, bool brin) {
+    LimbKernel kernel = nullptr;
+    ((log_r == (unsigned)LR ? (void)(kernel = inverse ? limb_kernel<true, LR>(scale_mode, last, brin) : limb_kernel<false, LR>(scale_mode, last, brin))
+                            : (void)0), ...);
+    return kernel;
+}
+constexpr auto limb_kernel_of = limb_kernel_among<12, 10, 9, 8, 7, 6, 5, 4>;  // the shapes of limb_supported
+
 struct BrinArgs {  // the bit-reversed coefficient source of a coset LDE's first pass + where its natural-order copy goes (nttl.hpp BRIN)
     const u64 *src = nullptr;
     size_t src_stride = 0;
     u64 *nat = nullptr;
     size_t nat_stride = 0;
 };
-static int launch_limb_pass(p2hot_ctx *ctx, const ntt::PassArgs &a, bool inverse, const u64 *twid, unsigned xcd_remap,
-                            unsigned zloop, dim3 grid, u64 last_const, const u64 *srow2, const nttl::W2 *sbase,
-                            const BrinArgs *brin = nullptr) {
+// One DIF chain: natural-order input -> bit-reversed output (per polynomial, per z slice).  `first` holds what the caller decides
+// of the first pass: it reads `in` (in_z_stride stays 0: every z slice reads the same polynomials), scales by scale_mode
+// (SCALE_CONST: scale_const, SCALE_TABLE: the coset scale tables) and writes `out`; later passes run in place on `out`.
+struct DifJob {
+    ntt::PassArgs first{};
+    size_t batch = 0, zcount = 1;
+    const u64 *srow2 = nullptr;  // coset_scale_tables: the tile-shaped tables of a strided limb pass (beside first.srow / first.scol)
+    const nttl::W2 *sbase = nullptr;
+    bool canon_last = false;  // the last pass stores canonical representatives
+    BrinArgs brin;            // optional (src != null): see coset_lde_impl
+};
+
+// launches pass i of the plan, a limb pass; `last_const` != 1 multiplies every output of this (last) pass by it (the 1/n of the
+// inverse transform)
+static int launch_limb_pass(p2hot_ctx *ctx, const NttPlan &plan, size_t i, const DifJob &job, const ntt::PassArgs &a, bool inverse,
+                            dim3 grid, unsigned xcd_remap, unsigned zloop, u64 last_const) {
+    const Pass &ps = plan.passes[i];
     nttl::LimbPassArgs ra{};
     ra.a = a;
-    if (brin && brin->src) {
-        ra.brin_src = brin->src;
-        ra.brin_stride = brin->src_stride;
-        ra.nat_out = brin->nat;
-        ra.nat_stride = brin->nat_stride;
+    if (i == 0 && job.brin.src) {
+        if (!plan.lde_reads_bitrev || inverse || a.scale_mode != ntt::SCALE_TABLE)
+            P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: the bit-reversed source belongs to the first pass of a two-pass coset LDE");
+        ra.brin_src = job.brin.src, ra.brin_stride = job.brin.src_stride;
+        ra.nat_out = job.brin.nat, ra.nat_stride = job.brin.nat_stride;
     }
-    ra.twid = twid;
-    ra.xcd_remap = xcd_remap;
-    ra.zloop = zloop;
+    P2_TRY(interpass_twiddles(ctx, inverse, ps, &ra.twid));
+    ra.xcd_remap = xcd_remap, ra.zloop = zloop;
     p2hot_ctx::LimbTables lt;
-    P2_TRY(limb_tables(ctx, inverse, a.log_r, &lt));
-    ra.tw_all = lt.tw_all;
-    ra.ufac = lt.ufac;
+    P2_TRY(limb_tables(ctx, inverse, ps.log_r, &lt));
+    ra.tw_all = lt.tw_all, ra.ufac = lt.ufac;
     // a workgroup of the contiguous pass keeps its staged tables for several tiles
-    ra.tiles_log = 0;
-    if (a.log_c == 0)
+    if (ps.log_c == 0)
         while (ra.tiles_log < ctx->limb_tiles_log && (grid.x >> (ra.tiles_log + 1)) >= 1 &&
                (size_t)(grid.x >> (ra.tiles_log + 1)) * grid.y * grid.z >= 4096)
             ++ra.tiles_log;
@@ -747,188 +888,73 @@ static int launch_limb_pass(p2hot_ctx *ctx, const ntt::PassArgs &a, bool inverse
     ra.wlast[1] = gl::canon(gl::mul(last_const, nttl::B1));
     ra.wlast[2] = gl::canon(gl::mul(last_const, nttl::B2));
     ra.wlast[3] = gl::canon(gl::mul(last_const, nttl::B3));
-    const size_t shm = nttl::limb_shmem_bytes((int)a.log_r);
-    if (wlast && !(a.log_r == 12 && a.scale_mode == ntt::SCALE_NONE)) P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: a final constant needs the contiguous pass");
-    ra.srow2 = srow2;
-    ra.sbase = sbase;
-    // the last conversion multiplies by 1 (LAST_UNIT), by a constant (LAST_CONST: the inverse transform's 1/n) or -- the
-    // strided first pass of a coset LDE -- by the tile's share of the coset scale (LAST_TILE)
-#define P2_LIMB(INVF, LR, MODE, LASTM)                                                                     \
-    do {                                                                                                   \
-        auto kfn_ = nttl::ntt_limbpass_kernel<INVF, LR, 12 - LR, MODE, LASTM>;                             \
-        P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(kfn_), shm));                                \
-        P2HOT_LAUNCH(kfn_, grid, dim3(nttl::NT), shm, ctx->stream, ra);                                    \
-    } while (0)
-#define P2_LIMB_BRIN(LR)                                                                                             \
-    do {                                                                                                                 \
-        auto kfnb_ = nttl::ntt_limbpass_kernel<false, (LR) == 12 ? 8 : (LR), (LR) == 12 ? 4 : 12 - (LR), ntt::SCALE_TABLE, nttl::LAST_TILE, true>; \
-        P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(kfnb_), shm));                                             \
-        P2HOT_LAUNCH(kfnb_, grid, dim3(nttl::NT), shm, ctx->stream, ra);                                                 \
-    } while (0)
-#define P2_LIMB_DIR(LR, MODE, LASTM) do { if (inverse) P2_LIMB(true, LR, MODE, LASTM); else P2_LIMB(false, LR, MODE, LASTM); } while (0)
-#define P2_LIMB_MODE(LR)                                                                                          \
-    do {                                                                                                          \
-        if (a.scale_mode == ntt::SCALE_TABLE) {                                                                   \
-            if (LR == 12) P2_LIMB_DIR(LR, ntt::SCALE_TABLE, nttl::LAST_UNIT);                                     \
-            else if (ra.brin_src) P2_LIMB_BRIN(LR);                                                               \
-            else P2_LIMB_DIR(LR, ntt::SCALE_TABLE, nttl::LAST_TILE);                                              \
-        } else if (a.scale_mode == ntt::SCALE_CONST) P2_LIMB_DIR(LR, ntt::SCALE_CONST, nttl::LAST_UNIT);          \
-        else P2_LIMB_DIR(LR, ntt::SCALE_NONE, nttl::LAST_UNIT);                                                   \
-    } while (0)
-    if (a.scale_mode == ntt::SCALE_TABLE && a.log_r != 12 && (!srow2 || !sbase)) P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: missing coset scale tables");
-    if (a.canon_out && a.log_c) P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: a strided pass is never the last one and stores no canonical representatives");
-    if (ra.brin_src && (inverse || a.log_c == 0 || ra.tiles_log || a.scale_mode != ntt::SCALE_TABLE || a.log_nblk != a.log_r + 12))
-        P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: the bit-reversed source belongs to the first pass of a two-pass coset LDE");
-    if (wlast) {
-        if (inverse)
-            P2_LIMB(true, 12, ntt::SCALE_NONE, nttl::LAST_CONST);
-        else
-            P2_LIMB(false, 12, ntt::SCALE_NONE, nttl::LAST_CONST);
-        return P2HOT_OK;
-    }
-    switch (a.log_r) {
-        case 12: P2_LIMB_MODE(12); break;
-        case 10: P2_LIMB_MODE(10); break;
-        case 9: P2_LIMB_MODE(9); break;
-        case 8: P2_LIMB_MODE(8); break;
-        case 7: P2_LIMB_MODE(7); break;
-        case 6: P2_LIMB_MODE(6); break;
-        case 5: P2_LIMB_MODE(5); break;
-        case 4: P2_LIMB_MODE(4); break;
-        default: P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: unsupported tile 2^%u x 2^%u", a.log_r, a.log_c);
-    }
-#undef P2_LIMB_MODE
-#undef P2_LIMB_BRIN
-#undef P2_LIMB_DIR
-#undef P2_LIMB
+    ra.srow2 = job.srow2, ra.sbase = job.sbase;
+    const bool tile_scale = a.scale_mode == ntt::SCALE_TABLE && ps.log_c;
+    if (tile_scale && !(plan.first_limb_shape && job.srow2 && job.sbase)) P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: missing coset scale tables");
+    if (a.canon_out && ps.log_c) P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: a strided pass is never the last one and stores no canonical representatives");
+    const int last = wlast ? nttl::LAST_CONST : tile_scale ? nttl::LAST_TILE : nttl::LAST_UNIT;
+    const LimbKernel kernel = limb_kernel_of(inverse, ps.log_r, a.scale_mode, last, ra.brin_src != nullptr);
+    if (!kernel)
+        P2_FAIL(ctx, P2HOT_EINVAL, "limb pass: no kernel for a 2^%u x 2^%u tile with scale mode %d and last conversion %d", ps.log_r,
+                ps.log_c, a.scale_mode, last);
+    const size_t shm = nttl::limb_shmem_bytes((int)ps.log_r);
+    P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(kernel), shm));
+    P2HOT_LAUNCH(kernel, grid, dim3(nttl::NT), shm, ctx->stream, ra);
     return P2HOT_OK;
 }
 
-// Runs the DIF chain: natural-order input -> bit-reversed output (per polynomial, per z slice).
-// The first pass reads `in` (no z offset: every z slice reads the same polynomials) and writes
-// `out`; later passes run in place on `out`.
-static int run_dif(p2hot_ctx *ctx, const u64 *in, size_t in_stride, u64 *out, size_t out_stride, size_t out_z_stride,
-                   size_t batch, size_t zcount, unsigned log_n, const ntt::RootTable &roots, int scale_mode,
-                   u64 scale_const, const u64 *srow, const u64 *scol, bool canon_last, const u64 *srow2 = nullptr,
-                   const nttl::W2 *sbase = nullptr, const BrinArgs *brin = nullptr) {
-    if (batch == 0 || zcount == 0) return P2HOT_OK;
-    if (batch > 65535 || zcount > 65535) P2_FAIL(ctx, P2HOT_EINVAL, "batch %zu / z %zu exceed the grid limit", batch, zcount);
-    std::vector<Pass> passes = plan_passes(log_n, ctx->ntt_strided_bits);
-    unsigned log_nblk = log_n;
-    bool limb_all = ctx->use_limb && ctx->use_regpass && ctx->ntt_radix_bits == 3;  // every pass of this chain is a limb pass
-    for (const Pass &ps : passes) limb_all = limb_all && limb_supported(ps.log_r, ps.log_c);
-    limb_all = limb_all && log_n <= 24;  // strided limb passes take their inter-pass twiddles from the table (blocks <= 2^24)
-    for (size_t i = 0; i < passes.size(); ++i) {
-        ntt::PassArgs a{};
-        const bool first = i == 0;
-        a.in = first ? in : out;
-        a.out = out;
-        a.in_poly_stride = first ? in_stride : out_stride;
-        a.in_z_stride = first ? 0 : out_z_stride;
-        a.out_poly_stride = out_stride;
-        a.out_z_stride = out_z_stride;
-        a.log_n = log_n;
-        a.log_nblk = log_nblk;
-        a.log_r = passes[i].log_r;
-        a.log_c = passes[i].log_c;
-        a.roots = roots;
-        a.scale_mode = first ? scale_mode : ntt::SCALE_NONE;
-        a.scale_const = scale_const;
-        a.srow = srow;
-        a.scol = scol;
-        a.canon_out = (canon_last && i + 1 == passes.size()) ? 1 : 0;
-        const unsigned tiles_log = log_n - a.log_r - a.log_c;
-        dim3 grid(1u << tiles_log, (unsigned)batch, (unsigned)zcount);
-        size_t shmem = ((size_t)8) << (a.log_r + a.log_c);
-        // live timing per (transform, pass kind): the iNTT, the coset LDE (scale tables) and plain forward transforms apart
-        const bool inv_t = roots.lo == ctx->inv.lo, lde_t = scale_mode == ntt::SCALE_TABLE;
-        ProfScope ps(ctx, a.log_c ? (inv_t ? "ntt_intt_strided" : lde_t ? "ntt_lde_strided" : "ntt_fwd_strided")
-                                  : (inv_t ? "ntt_intt_contig" : lde_t ? "ntt_lde_contig" : "ntt_fwd_contig"));
-        if (ctx->use_regpass) {
-            ntt::RegPassArgs ra{};
-            ra.a = a;
-            const bool inverse = roots.lo == ctx->inv.lo;
-            // strided passes multiply by w_{n'}^(col * k1) on the way out: the same 2^log_nblk values for every block, polynomial
-            // and coset, kept as a table (<= 128 MiB) laid out like a block so that the load is as coalesced as the store
-            ra.twid = nullptr;
-            if (log_nblk > a.log_r && log_nblk <= 24) {
-                auto key = std::make_tuple((int)inverse, log_nblk, a.log_r);
-                auto it = ctx->twid_cache.find(key);
-                if (it == ctx->twid_cache.end()) {
-                    u64 *t = nullptr;
-                    P2_HIP(ctx, hipMalloc((void **)&t, (size_t)8 << log_nblk));
-                    P2HOT_LAUNCH(ntt::interpass_twiddle_kernel, dim3(cdiv((size_t)1 << log_nblk, 256)), dim3(256), 0, ctx->stream,
-                                 t, log_nblk, a.log_r, roots);
-                    P2_LAUNCH_CHECK(ctx);
-                    it = ctx->twid_cache.emplace(key, t).first;
-                }
-                ra.twid = it->second;
-            }
-            ra.local = inverse ? ctx->local_inv : ctx->local_fwd;
-            ra.inverse = inverse;
-            ra.xcd_remap = (ctx->ntt_xcd_remap && a.log_c && tiles_log >= 3) ? tiles_log : 0;
-            // rounds of radix <= 2^maxp, remainder split as evenly as possible.  Radix 8 with 512 threads
-            // (8 points per lane, <= 64 VGPRs, 8 waves/SIMD) measured faster than radix 16 with 256 threads:
-            // the pass is mostly VALU issue, and the extra waves cover the global / LDS / barrier waits.
-            const unsigned maxp = ctx->ntt_radix_bits;
-            unsigned rem = a.log_r, k = 0;
-            unsigned nr = (rem + maxp - 1) / maxp;
-            for (unsigned q = 0; q < nr; ++q) {
-                unsigned part = (rem + (nr - q) - 1) / (nr - q);
-                ra.rounds[k++] = part;
-                rem -= part;
-            }
-            size_t shm = (size_t)8 * ntt::TILE_WORDS_PADDED;
-            // every z slice (coset) reads the same input tile: one workgroup produces them all from one fetch -- when the
-            // launch has workgroups to spare.  A small launch keeps the cosets in grid.z instead: at 2^12 rows the loop made
-            // the LDE a chain of 8 tile transforms on 2..135 workgroups (95 us whatever the width; 5 such launches per proof)
-            if (first && zcount > 1 && a.in_z_stride == 0 && ((size_t)1 << tiles_log) * batch >= ctx->zloop_min_groups) {
-                ra.zloop = (unsigned)zcount;
-                grid.z = 1;
-            }
-            if (ctx->use_limb && maxp == 3 && limb_supported(a.log_r, a.log_c) && (a.log_c == 0 || ra.twid) &&
-                !(a.scale_mode == ntt::SCALE_TABLE && a.log_c && !srow2)) {
-                // the constant scale of an inverse transform moves from the first pass to the last conversion of the last
-                // pass (every output of a tile's last round is converted by a constant 4-form anyway: it becomes c * B^i)
-                u64 last_const = 1;
-                if (limb_all && scale_mode == ntt::SCALE_CONST) {
-                    ra.a.scale_mode = ntt::SCALE_NONE;
-                    if (i + 1 == passes.size()) last_const = scale_const;
-                }
-                P2_TRY(launch_limb_pass(ctx, ra.a, inverse, ra.twid, ra.xcd_remap, ra.zloop, grid, last_const, srow2, sbase, first ? brin : nullptr));
-                P2_LAUNCH_CHECK(ctx);
-                log_nblk -= a.log_r;
-                continue;
-            }
-            if (first && brin && brin->src) P2_FAIL(ctx, P2HOT_EINVAL, "run_dif: the bit-reversed source needs the limb passes");
-            if (maxp == 3) {  // one kernel per (direction, scale mode): the per-point mode tests are compiled out
-#define P2_NTT512C(INVF, MODE, CT) P2HOT_LAUNCH((ntt::ntt_regpass_kernel<INVF, 512, (CT) ? 8 : 6, MODE, CT>), grid, dim3(512), shm, ctx->stream, ra)
-#define P2_NTT512(INVF, MODE) do { if (a.log_c == 0 && log_nblk == a.log_r) P2_NTT512C(INVF, MODE, true); else P2_NTT512C(INVF, MODE, false); } while (0)
-                if (a.scale_mode == ntt::SCALE_TABLE) {
-                    if (inverse) P2_NTT512(true, ntt::SCALE_TABLE); else P2_NTT512(false, ntt::SCALE_TABLE);
-                } else if (a.scale_mode == ntt::SCALE_CONST) {
-                    if (inverse) P2_NTT512(true, ntt::SCALE_CONST); else P2_NTT512(false, ntt::SCALE_CONST);
-                } else {
-                    if (inverse) P2_NTT512(true, ntt::SCALE_NONE); else P2_NTT512(false, ntt::SCALE_NONE);
-                }
-#undef P2_NTT512C
-#undef P2_NTT512
-            } else {
-                if (inverse)
-                    P2HOT_LAUNCH((ntt::ntt_regpass_kernel<true, 256, 4>), grid, dim3(256), shm, ctx->stream, ra);
-                else
-                    P2HOT_LAUNCH((ntt::ntt_regpass_kernel<false, 256, 4>), grid, dim3(256), shm, ctx->stream, ra);
-            }
-        } else {
-            P2HOT_LAUNCH(ntt::ntt_pass_kernel, grid, dim3(ntt::THREADS), shmem, ctx->stream, a);
+// Runs the DIF chain of the job under the plan
+static int run_dif(p2hot_ctx *ctx, const NttPlan &plan, unsigned log_n, bool inverse, const DifJob &job) {
+    if (job.batch == 0 || job.zcount == 0) return P2HOT_OK;
+    if (job.batch > 65535 || job.zcount > 65535) P2_FAIL(ctx, P2HOT_EINVAL, "batch %zu / z %zu exceed the grid limit", job.batch, job.zcount);
+    if (job.brin.src && !plan.lde_reads_bitrev) P2_FAIL(ctx, P2HOT_EINVAL, "run_dif: the bit-reversed source needs the limb passes");
+    // live timing per (transform, pass kind): the iNTT, the coset LDE (scale tables) and plain forward transforms apart
+    const bool lde = job.first.scale_mode == ntt::SCALE_TABLE;
+    const char *strided_name = inverse ? "ntt_intt_strided" : lde ? "ntt_lde_strided" : "ntt_fwd_strided";
+    const char *contig_name = inverse ? "ntt_intt_contig" : lde ? "ntt_lde_contig" : "ntt_fwd_contig";
+    for (size_t i = 0; i < plan.passes.size(); ++i) {
+        const Pass &ps = plan.passes[i];
+        const bool first = i == 0, last = i + 1 == plan.passes.size();
+        ntt::PassArgs a = job.first;
+        if (!first) {
+            a.in = a.out;
+            a.in_poly_stride = a.out_poly_stride, a.in_z_stride = a.out_z_stride;
+            a.scale_mode = ntt::SCALE_NONE;
+        }
+        a.log_n = log_n, a.log_nblk = ps.log_nblk;
+        a.log_r = ps.log_r, a.log_c = ps.log_c;
+        a.roots = inverse ? ctx->inv : ctx->fwd;
+        a.canon_out = job.canon_last && last;
+        // the constant scale of an inverse transform moves from the first pass to the last conversion of the last limb
+        // pass (every output of a tile's last round is converted by a constant 4-form anyway: it becomes c * B^i)
+        u64 last_const = 1;
+        if (plan.limb_all && job.first.scale_mode == ntt::SCALE_CONST) {
+            a.scale_mode = ntt::SCALE_NONE;
+            if (last) last_const = a.scale_const;
+        }
+        const unsigned tiles_log = log_n - ps.log_r - ps.log_c;
+        dim3 grid(1u << tiles_log, (unsigned)job.batch, (unsigned)job.zcount);
+        const unsigned xcd_remap = (ctx->ntt_xcd_remap && ps.log_c && tiles_log >= 3) ? tiles_log : 0;
+        // every z slice (coset) reads the same input tile: one workgroup produces them all from one fetch -- when the
+        // launch has workgroups to spare.  A small launch keeps the cosets in grid.z instead: at 2^12 rows the loop made
+        // the LDE a chain of 8 tile transforms on 2..135 workgroups (95 us whatever the width; 5 such launches per proof)
+        unsigned zloop = 0;
+        if (ps.kernel != PASS_LDS && first && job.zcount > 1 && ((size_t)1 << tiles_log) * job.batch >= ctx->zloop_min_groups) {
+            zloop = (unsigned)job.zcount;
+            grid.z = 1;
+        }
+        ProfScope prof(ctx, ps.log_c ? strided_name : contig_name);
+        switch (ps.kernel) {
+            case PASS_LIMB: P2_TRY(launch_limb_pass(ctx, plan, i, job, a, inverse, grid, xcd_remap, zloop, last_const)); break;
+            case PASS_WORD: P2_TRY(launch_word_pass(ctx, ps, a, inverse, grid, xcd_remap, zloop)); break;
+            case PASS_LDS:
+                P2HOT_LAUNCH(ntt::ntt_pass_kernel, grid, dim3(ntt::THREADS), (size_t)8 << (ps.log_r + ps.log_c), ctx->stream, a);
+                break;
         }
         P2_LAUNCH_CHECK(ctx);
-        log_nblk -= a.log_r;
     }
     return P2HOT_OK;
 }
-
-static unsigned first_pass_log_r(const p2hot_ctx *ctx, unsigned log_n) { return plan_passes(log_n, ctx->ntt_strided_bits)[0].log_r; }
 
 static size_t bitrev_sz(size_t x, unsigned bits) {
     size_t r = 0;
@@ -967,9 +993,12 @@ static int ntt_natural(p2hot_ctx *ctx, u64 *d_data, size_t batch, size_t stride,
     if (!d_data || stride < n) P2_FAIL(ctx, P2HOT_EINVAL, "ntt: null data or stride < n");
     u64 *tmp;
     P2_TRY(scratch_get(ctx, 0, batch * n * 8, (void **)&tmp));
-    u64 n_inv = gl::inv(n % gl::P);
-    P2_TRY(run_dif(ctx, d_data, stride, tmp, n, 0, batch, 1, log_n, inverse ? ctx->inv : ctx->fwd,
-                   inverse ? ntt::SCALE_CONST : ntt::SCALE_NONE, n_inv, nullptr, nullptr, false));
+    DifJob job;
+    job.first.in = d_data, job.first.in_poly_stride = stride;
+    job.first.out = tmp, job.first.out_poly_stride = n;
+    job.batch = batch;
+    if (inverse) job.first.scale_mode = ntt::SCALE_CONST, job.first.scale_const = gl::inv(n % gl::P);
+    P2_TRY(run_dif(ctx, plan_ntt(ctx, log_n), log_n, inverse, job));
     return launch_bitrev(ctx, tmp, d_data, batch, n, stride, log_n);
 }
 
@@ -1003,14 +1032,14 @@ extern "C" int p2hot_coset_ifft_dev(p2hot_ctx *ctx, uint64_t *d_data, size_t bat
 
 // scale tables for row blocks [b0, b0 + zc): block b is coset j = bitrev_rb(b), s_b = shift * w_N^j;
 // srow[z][i] = s_b^(i * stride), scol[z][base] = s_b^base
-static int coset_scale_tables(p2hot_ctx *ctx, unsigned log_n, unsigned rate_bits, u64 shift, size_t b0, size_t zc,
-                              const u64 **srow, const u64 **scol, const u64 **srow2, const nttl::W2 **sbase) {
-    const Pass first = plan_passes(log_n, ctx->ntt_strided_bits)[0];
+static int coset_scale_tables(p2hot_ctx *ctx, const NttPlan &plan, unsigned log_n, unsigned rate_bits, u64 shift, size_t b0,
+                              size_t zc, DifJob *job) {
+    const Pass &first = plan.passes[0];
     const unsigned log_r = first.log_r;
     auto key = std::make_tuple(log_n, rate_bits, shift, b0, zc, log_r);
     const size_t R = (size_t)1 << log_r, stride = (size_t)1 << (log_n - log_r);
     // a strided limb first pass takes the scale as a tile-shaped (row, column-in-tile) table plus one 4-form per tile
-    const bool limb = first.log_c > 0 && limb_supported(first.log_r, first.log_c);
+    const bool limb = plan.first_limb_shape;
     const size_t tiles = limb ? stride >> first.log_c : 0;
     const size_t words = zc * (R + stride) + (limb ? zc * ((size_t)4096 + tiles * 4) : 0);
     auto it = ctx->scale_cache.find(key);
@@ -1036,35 +1065,17 @@ static int coset_scale_tables(p2hot_ctx *ctx, unsigned log_n, unsigned rate_bits
         P2_LAUNCH_CHECK(ctx);
         ctx->scale_cache[key] = t;
     }
-    *srow = t;
-    *scol = t + zc * R;
-    *srow2 = limb ? t + zc * (R + stride) : nullptr;
-    *sbase = limb ? reinterpret_cast<const nttl::W2 *>(t + zc * (R + stride) + zc * 4096) : nullptr;
+    job->first.srow = t;
+    job->first.scol = t + zc * R;
+    job->srow2 = limb ? t + zc * (R + stride) : nullptr;
+    job->sbase = limb ? reinterpret_cast<const nttl::W2 *>(t + zc * (R + stride) + zc * 4096) : nullptr;
     return P2HOT_OK;
 }
 
-// can the coset LDE of 2^log_n coefficients read them from the inverse transform's bit-reversed output (nttl.hpp BRIN)?  Two passes,
-// both limb passes, inter-pass twiddles from the table: exactly the conditions under which run_dif launches the limb kernels
-static bool lde_can_read_bitrev(const p2hot_ctx *ctx, unsigned log_n) {
-    if (!ctx->lde_reads_bitrev || !(ctx->use_limb && ctx->use_regpass && ctx->ntt_radix_bits == 3) || log_n > 24) return false;
-    const std::vector<Pass> passes = plan_passes(log_n, ctx->ntt_strided_bits);
-    return passes.size() == 2 && passes[0].log_c > 0 && limb_supported(passes[0].log_r, passes[0].log_c) &&
-           limb_supported(passes[1].log_r, passes[1].log_c);
-}
-
+// `brin` (optional, src != null): the coefficients come from brin.src in bit-reversed order instead of d_coeffs (which may then be
+// the same pointer as brin.nat: nothing reads it), and the first pass leaves their natural-order, canonical copy in brin.nat
 static int coset_lde_impl(p2hot_ctx *ctx, const uint64_t *d_coeffs, size_t W, size_t coeff_stride, unsigned log_n, unsigned rate_bits,
-                          uint64_t shift, size_t row_begin, size_t row_count, uint64_t *d_lde, size_t lde_stride, const BrinArgs *brin);
-
-extern "C" int p2hot_coset_lde_dev(p2hot_ctx *ctx, const uint64_t *d_coeffs, size_t W, size_t coeff_stride,
-                                   unsigned log_n, unsigned rate_bits, uint64_t shift, size_t row_begin,
-                                   size_t row_count, uint64_t *d_lde, size_t lde_stride) {
-    return coset_lde_impl(ctx, d_coeffs, W, coeff_stride, log_n, rate_bits, shift, row_begin, row_count, d_lde, lde_stride, nullptr);
-}
-
-// `brin` (optional): the coefficients come from brin->src in bit-reversed order instead of d_coeffs (which may then be the same
-// pointer as brin->nat: nothing reads it), and the first pass leaves their natural-order, canonical copy in brin->nat
-static int coset_lde_impl(p2hot_ctx *ctx, const uint64_t *d_coeffs, size_t W, size_t coeff_stride, unsigned log_n, unsigned rate_bits,
-                          uint64_t shift, size_t row_begin, size_t row_count, uint64_t *d_lde, size_t lde_stride, const BrinArgs *brin) {
+                          uint64_t shift, size_t row_begin, size_t row_count, uint64_t *d_lde, size_t lde_stride, const BrinArgs &brin) {
     if (!ctx) return P2HOT_EINVAL;
     DeviceGuard dev_guard_(ctx);
     P2_TRY(check_log(ctx, log_n + rate_bits, "coset_lde"));
@@ -1075,11 +1086,22 @@ static int coset_lde_impl(p2hot_ctx *ctx, const uint64_t *d_coeffs, size_t W, si
     if (row_begin % n || row_count % n || row_begin + row_count > N)
         P2_FAIL(ctx, P2HOT_EINVAL, "coset_lde: rows [%zu,+%zu) are not whole coset blocks of %zu", row_begin, row_count, n);
     const size_t b0 = row_begin >> log_n, zc = row_count >> log_n;
-    const u64 *srow, *scol, *srow2;
-    const nttl::W2 *sbase;
-    P2_TRY(coset_scale_tables(ctx, log_n, rate_bits, shift, b0, zc, &srow, &scol, &srow2, &sbase));
-    return run_dif(ctx, d_coeffs, coeff_stride, d_lde, lde_stride, n, W, zc, log_n, ctx->fwd, ntt::SCALE_TABLE, 0, srow,
-                   scol, true, srow2, sbase, brin);
+    const NttPlan plan = plan_ntt(ctx, log_n);
+    DifJob job;
+    job.first.in = d_coeffs, job.first.in_poly_stride = coeff_stride;
+    job.first.out = d_lde, job.first.out_poly_stride = lde_stride, job.first.out_z_stride = n;
+    job.batch = W, job.zcount = zc;
+    job.first.scale_mode = ntt::SCALE_TABLE;
+    P2_TRY(coset_scale_tables(ctx, plan, log_n, rate_bits, shift, b0, zc, &job));
+    job.canon_last = true;
+    job.brin = brin;
+    return run_dif(ctx, plan, log_n, false, job);
+}
+
+extern "C" int p2hot_coset_lde_dev(p2hot_ctx *ctx, const uint64_t *d_coeffs, size_t W, size_t coeff_stride,
+                                   unsigned log_n, unsigned rate_bits, uint64_t shift, size_t row_begin,
+                                   size_t row_count, uint64_t *d_lde, size_t lde_stride) {
+    return coset_lde_impl(ctx, d_coeffs, W, coeff_stride, log_n, rate_bits, shift, row_begin, row_count, d_lde, lde_stride, BrinArgs{});
 }
 
 // rev_bits > 0: row r of the column-major matrix lands in row reverse_bits(r, rev_bits) of the row-major one (rows == 2^rev_bits):
@@ -1360,12 +1382,17 @@ static int commit_dev_impl(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_st
             if (!d_coeffs || coeff_stride < n) P2_FAIL(ctx, P2HOT_EINVAL, "commit: d_coeffs is required for from_values");
             u64 *tmp;
             P2_TRY(scratch_get(ctx, 0, W * n * 8, (void **)&tmp));
-            P2_TRY(run_dif(ctx, d_cols, col_stride, tmp, n, 0, W, 1, log_n, ctx->inv, ntt::SCALE_CONST,
-                           gl::inv(n % gl::P), nullptr, nullptr, false));
+            const NttPlan plan = plan_ntt(ctx, log_n);
+            DifJob job;
+            job.first.in = d_cols, job.first.in_poly_stride = col_stride;
+            job.first.out = tmp, job.first.out_poly_stride = n;
+            job.batch = W;
+            job.first.scale_mode = ntt::SCALE_CONST, job.first.scale_const = gl::inv(n % gl::P);
+            P2_TRY(run_dif(ctx, plan, log_n, true, job));
             // the bit reversal into `polynomials` order: its own kernel, or -- when the LDE below is ONE launch sequence of two limb
             // passes -- folded into the LDE's first pass, which reads the bit-reversed array and writes the natural copy itself
             const bool one_lde = !(ctx->overlap && (row_count >> log_n) > 1 && row_count % n == 0);
-            if (one_lde && row_count > 0 && lde_can_read_bitrev(ctx, log_n)) {
+            if (one_lde && row_count > 0 && plan.lde_reads_bitrev) {
                 brin.src = tmp;
                 brin.src_stride = n;
                 brin.nat = d_coeffs;
@@ -1409,7 +1436,7 @@ static int commit_dev_impl(p2hot_ctx *ctx, const uint64_t *d_cols, size_t col_st
     {
         (void)blocks;
         P2_TRY(coset_lde_impl(ctx, coeff_src, W, coeff_src_stride, log_n, rate_bits, gl::COSET_SHIFT, row_begin, row_count, d_lde,
-                              lde_stride, brin.src ? &brin : nullptr));
+                              lde_stride, brin));
         P2_TRY(merkle_dev_impl(ctx, d_lde, 0, lde_stride, W, log_N, cap_height, row_begin, row_count, d_digests, d_cap, hash_n));
     }
     if (d_leaves) P2_TRY(p2hot_transpose_dev(ctx, d_lde, lde_stride, W, row_count, d_leaves));

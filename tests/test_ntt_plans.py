@@ -1,12 +1,12 @@
 """Every NTT pass plan and kernel variant against a plain transform (tests/ntt_ref.py), not only against the oracle.
 
-run_dif (p2hot.hip) picks its kernels from the size, the batch, the coset count and the context's knobs:
+plan_ntt (p2hot.hip) picks every pass's kernel from the size and the context's knobs, run_dif launches them:
   * plan_passes(log_n, P2HOT_NTT_STRIDED_BITS): strided passes of log_r bits, then the 12-bit contiguous pass;
-  * limb_supported: strided log_r 4..10 and the contiguous pass run nttl::ntt_limbpass_kernel (one instantiation per log_r), strided
+  * limb_supported (Pass::kernel): strided log_r 4..10 and the contiguous pass run nttl::ntt_limbpass_kernel (one instantiation per log_r), strided
     log_r 1..3 and 11 the word-based ntt_regpass_kernel; above 2^24 the first pass has no inter-pass table and runs the word kernel;
-  * limb_all (every pass a limb pass, log_n <= 24) moves the inverse's 1/n from the first pass (SCALE_CONST) to the last (LAST_CONST);
+  * NttPlan::limb_all (every pass a limb pass, log_n <= 24) moves the inverse's 1/n from the first pass (SCALE_CONST) to the last (LAST_CONST);
   * the coset LDE's first pass scales by a table (LAST_TILE when strided, LAST_UNIT when contiguous), may read a bit-reversed source
-    (from_values, P2HOT_LDE_BITREV_SRC) and loops over the cosets in one workgroup (zloop, P2HOT_NTT_ZLOOP_MIN);
+    (from_values, NttPlan::lde_reads_bitrev, P2HOT_LDE_BITREV_SRC) and loops over the cosets in one workgroup (zloop, P2HOT_NTT_ZLOOP_MIN);
   * the contiguous limb pass stages its tables once for 2^tiles_log tiles (P2HOT_LIMB_TILES_LOG) when >= 4096 workgroups remain;
   * P2HOT_NTT_XCD_REMAP, P2HOT_NTT_LIMB and p2hot_tune_ntt modes 0 / 4 / 8 / 3.
 Each knob variant runs on a context of its own (environment set, engine made, environment restored).  Inputs stress the limb
@@ -76,7 +76,7 @@ def plan(log_n, strided_bits=10):
 
 
 def kernels(log_n, strided_bits=10):
-    """which kernel run_dif launches per pass (default knobs): 'limb' or 'word'"""
+    """which kernel plan_ntt gives each pass (Pass::kernel, default knobs): 'limb' or 'word'"""
     out, nblk = [], log_n
     for i, r in enumerate(plan(log_n, strided_bits)):
         strided = i + 1 < len(plan(log_n, strided_bits))
@@ -420,6 +420,39 @@ def test_from_values_lde_bit_reversed_source(eng, ora, log_n, bitrev_src):
         assert int(coeffs[c, n // 3]) == ntt_ref.fft_at(vals[c], n // 3, inverse=True)
     exp = lde_expected_blocks(coeffs, log_n, rb, pyref.G, 0, 1 << rb, ora)
     assert (lde == exp).all(), (log_n, bitrev_src)
+    assert int(lde[0, N - 5]) == ntt_ref.lde_row_at(coeffs[0], rb, pyref.G, N - 5)
+
+
+@pytest.mark.parametrize("log_n,bits,mode,reads_bitrev", [(13, 10, 3, False), (16, 10, 3, True), (19, 6, 3, False),
+                                                          (16, 10, 0, False), (16, 10, 4, False), (16, 10, 8, False)])
+def test_from_values_bit_reversal_follows_the_plan(eng, ora, log_n, bits, mode, reads_bitrev):
+    """from_values skips the stand-alone bit reversal exactly when the planned LDE is two limb passes (NttPlan::lde_reads_bitrev, read by
+    commit_dev_impl and run_dif alike): [1, 12] = word, limb and [4, 3, 12] = limb, word, limb run it, [4, 12] = limb, limb does not --
+    unless p2hot_tune_ntt 0 / 4 / 8 switches the limb kernels off.  The smallest size of every branch; coefficients and LDE rows
+    against ntt_ref / the oracle each time"""
+    ks = kernels(log_n, bits) if mode == 3 else ["word"] * len(plan(log_n, bits))
+    assert (ks == ["limb", "limb"]) == reads_bitrev, (plan(log_n, bits), ks)
+    e = variant(eng) if bits == 10 else variant(eng, NTT_STRIDED_BITS=bits)
+    rng = np.random.default_rng(50 + log_n + mode)
+    n, W, rb = 1 << log_n, 2, 1
+    vals = rand_field(rng, W, n, noncanonical=True)
+    N = n << rb
+    try:
+        e.check(e.lib.p2hot_tune_ntt(e.ctx, mode))
+        e.profile(True)
+        e.profile_results(reset=True)
+        r = e.commit(e.dev(vals), log_n, rb, N.bit_length() - 1, True)
+        coeffs, lde = e.host(r["coeffs"]), e.host(r["lde"])
+        prof = e.profile_results(reset=True)
+        e.profile(False)
+    finally:
+        e.check(e.lib.p2hot_tune_ntt(e.ctx, 3))
+    assert ("bitrev_permute" in prof) == (not reads_bitrev), (ks, prof)
+    for c in range(W):
+        assert (coeffs[c] == ntt_ref.reduce(ora.ifft(vals[c].copy()))).all(), (log_n, mode, c)
+        assert int(coeffs[c, n // 3]) == ntt_ref.fft_at(vals[c], n // 3, inverse=True)
+    exp = lde_expected_blocks(coeffs, log_n, rb, pyref.G, 0, 1 << rb, ora)
+    assert (lde == exp).all(), (log_n, bits, mode)
     assert int(lde[0, N - 5]) == ntt_ref.lde_row_at(coeffs[0], rb, pyref.G, N - 5)
 
 
