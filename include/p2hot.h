@@ -170,13 +170,27 @@ typedef struct {
     uint32_t input_len, output_len;
 } p2hot_challenger_state;
 typedef struct p2hot_challenger p2hot_challenger;
-int p2hot_challenger_create(p2hot_ctx *ctx, p2hot_challenger **out); /* Challenger::new */
+int p2hot_challenger_create(p2hot_ctx *ctx, p2hot_challenger **out); /* Challenger::<F, PoseidonHash>::new */
+/* Challenger::<F, KeccakHash<hash_size>>::new (KeccakGoldilocksConfig: hash_size = 25): the same handle, state layout and
+ * load / store / step / destroy; the duplex (challenger.rs:129-144) runs KeccakPermutation (hash/keccak.rs:63-94: the state's 96
+ * canonical bytes through a chain of Keccak-256 hashes, every output word >= p dropped).  hash_size is 1..32, else P2HOT_EINVAL.
+ * The Keccak duplex is a chain of three dependent Keccak-f and runs on one lane: about 37 us per duplex, i.e. per 8 observed
+ * elements (the Poseidon one: 10 us), so observing a long vector -- the final polynomial of a schedule with few reduction rounds,
+ * a large final_poly_coeff_len -- costs that much per 8 elements on a single GPU thread.
+ * The handle records its hasher: it is what selects the Keccak FRI trees and grind in p2hot_fri_commit / _dev, p2hot_fri_pow and
+ * p2hot_prove_openings. */
+int p2hot_challenger_create_keccak(p2hot_ctx *ctx, unsigned hash_size, p2hot_challenger **out);
 void p2hot_challenger_destroy(p2hot_challenger *ch);
 int p2hot_challenger_load(p2hot_challenger *ch, const p2hot_challenger_state *host_state);
 int p2hot_challenger_store(p2hot_challenger *ch, p2hot_challenger_state *host_state);
 /* observe_elements (challenger.rs:50-54) then get_n_challenges (:93-95); host pointers; either count may be 0 */
 int p2hot_challenger_step(p2hot_challenger *ch, const uint64_t *observe, size_t n_observe, uint64_t *challenges,
                           size_t n_challenges);
+/* observe_hash / observe_cap (challenger.rs:69-80) of `count` digests given as their 32-byte slots (host [count][4]): the
+ * elements of GenericHashOut::to_vec.  A Poseidon challenger observes the 4 words of each; a KeccakHash<N> challenger the
+ * ceil(N / 7) seven-byte chunks of bytes 0..N, each zero-extended to a word (hash_types.rs:184-194: 4 elements for N = 25, 5 for
+ * N = 32); bytes N..32 of a slot are ignored. */
+int p2hot_challenger_observe_digests(p2hot_challenger *ch, const uint64_t *slots, size_t count);
 
 /* ---------------------------------------------------------------- FRI commit phase */
 /* fri_committed_trees (fri/prover.rs:84-150) including the `lde_final_values` coset FFT of
@@ -191,7 +205,11 @@ int p2hot_challenger_step(p2hot_challenger *ch, const uint64_t *observe, size_t 
  *     digests_out  4 * p2hot_num_digests(log m_r - arity_bits[r], cap_height) words per round
  *     caps_out     4 << cap_height words per round
  *     betas_out    2 words per round
- *     final_out    [(m_last >> rate_bits)][2], m_last = N >> sum(arity_bits) */
+ *     final_out    [(m_last >> rate_bits)][2], m_last = N >> sum(arity_bits)
+ * The round trees are built by the challenger's hasher: with a Keccak challenger (p2hot_challenger_create_keccak) they are
+ * KeccakHash<N> trees (digests and caps in 32-byte slots, bytes N..32 zero; hash_or_noop copies a leaf of 8 * W <= N bytes, which
+ * happens for N = 32 at arity 2), each cap is observed as BytesHash<N> digests, and the dummy caps of max_num_query_steps are 4 zero
+ * elements per entry whatever the hasher (fri/prover.rs:126). */
 int p2hot_fri_commit(p2hot_ctx *ctx, const uint64_t *coeffs, unsigned log_n, unsigned rate_bits,
                      unsigned cap_height, const unsigned *arity_bits, unsigned n_rounds,
                      unsigned max_num_query_steps, size_t final_poly_coeff_len,
@@ -248,7 +266,7 @@ int p2hot_merkle_paths_dev(p2hot_ctx *ctx, const uint64_t *d_digests, unsigned l
                            const uint64_t *d_idx, size_t m, uint64_t *d_out);
 /* fri_proof_of_work (fri/prover.rs:153-202), deterministic: returns the SMALLEST valid witness
  * (the reference's rayon find_any returns an arbitrary valid one), observes it and draws the
- * response like the reference does. */
+ * response like the reference does.  The candidates go through the challenger's permutation (Poseidon or KeccakPermutation). */
 int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bits, uint64_t *witness_out);
 
 /* ================================================================ prover session (HOST pointers)
@@ -287,7 +305,8 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
 #define P2HOT_LEAVES_NATURAL 8u
 /* p2hot_commit / _salted / _cols: the Merkle tree's hasher in bits 8..15 of the flag word.  0 = PoseidonHash; n = 1..32 =
  * KeccakHash<n> (digests in 32-byte slots, see p2hot_keccak_merkle_dev); 33..255 is P2HOT_EINVAL.  The batch records its hasher:
- * p2hot_prove_openings / _many refuse a Keccak batch with P2HOT_EUNSUPPORTED (FRI for the Keccak config stays on the CPU);
+ * p2hot_prove_openings opens Keccak batches with a Keccak challenger of the same n (see there); _many and the multi-GPU entry
+ * points refuse them with P2HOT_EUNSUPPORTED;
  * p2hot_batch_rows / _paths / _digests / _coeffs, p2hot_eval_openings and p2hot_quotient_polys do not depend on the hasher. */
 #define P2HOT_HASH_KECCAK(n) ((unsigned)(n) << 8)
 #define P2HOT_HASH_MASK 0xFF00u
@@ -447,7 +466,13 @@ int p2hot_fri_proof_sizes(const p2hot_batch *const *oracles, size_t n_oracles, c
 /* PolynomialBatch::prove_openings (fri/oracle.rs:176-237) + fri_proof (fri/prover.rs:24-82): alpha, final_poly =
  * sum_i alpha^(k_i) (F_i - F_i(z_i)) / (X - z_i), its LDE, the commit phase (fri_committed_trees, :84-150), the
  * proof-of-work grind (:153-202, smallest witness) and the query rounds (:204-258), with the transcript advanced exactly
- * like the reference.  All oracles must share degree, rate and cap height. */
+ * like the reference.  All oracles must share degree, rate and cap height.
+ * The hasher is the config's (Challenger<F, C::Hasher>): either a Poseidon challenger and Poseidon oracles, or a KeccakHash<n>
+ * challenger (p2hot_challenger_create_keccak) and KeccakHash<n> oracles (P2HOT_HASH_KECCAK(n)) of the same n -- then the round
+ * trees, the transcript and the grind are Keccak, and digests / path entries are the 32-byte slots, bytes n..32 zero.  Any mixture
+ * (Poseidon challenger with a Keccak oracle, Keccak challenger with a Poseidon oracle, different n) is P2HOT_EUNSUPPORTED before
+ * anything is enqueued.  p2hot_prove_openings_many, p2hot_group_prove_openings and the sharded commits stay Poseidon-only: a Keccak
+ * challenger or oracle there is P2HOT_EUNSUPPORTED. */
 int p2hot_prove_openings(p2hot_ctx *ctx, const p2hot_fri_batch_info *batches, size_t n_batches,
                          const p2hot_batch *const *oracles, size_t n_oracles, p2hot_challenger *challenger,
                          const p2hot_fri_params *params, p2hot_fri_proof *proof);

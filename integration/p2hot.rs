@@ -231,6 +231,8 @@ extern "C" {
     ) -> c_int;
     // ---- Challenger
     pub fn p2hot_challenger_create(ctx: *mut P2hotCtx, out: *mut *mut P2hotChallenger) -> c_int;
+    pub fn p2hot_challenger_create_keccak(ctx: *mut P2hotCtx, hash_size: c_uint, out: *mut *mut P2hotChallenger) -> c_int;
+    pub fn p2hot_challenger_observe_digests(ch: *mut P2hotChallenger, slots: *const u64, count: usize) -> c_int;
     pub fn p2hot_challenger_destroy(ch: *mut P2hotChallenger);
     pub fn p2hot_challenger_load(ch: *mut P2hotChallenger, host_state: *const P2hotChallengerState) -> c_int;
     pub fn p2hot_challenger_store(ch: *mut P2hotChallenger, host_state: *mut P2hotChallengerState) -> c_int;
@@ -477,8 +479,9 @@ pub fn applies<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D
 
 /// Does the GPU commitment apply to this instantiation with a Keccak tree?  KeccakGoldilocksConfig (plonk/config.rs:118-126,
 /// `Hasher = KeccakHash<25>`: the outer proof of a recursion chain) gets the LDE and the KeccakHash<25> tree of from_values /
-/// from_coeffs on the GPU (`commit_keccak`).  `applies` stays false for it, so FRI, the grind, the challenger and the quotient
-/// take the CPU bodies.
+/// from_coeffs on the GPU (`commit_keccak`), and its opening proofs too (`applies_fri`: `prove_openings`, `fri_committed_trees`
+/// with the library's Keccak challenger, Keccak round trees and Keccak grind).  `applies` stays false for it, so the partial
+/// products, the quotient and the openings' evaluation take the CPU bodies.
 pub fn applies_keccak_commit<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>() -> bool {
     enabled()
         && D == 2
@@ -486,6 +489,22 @@ pub fn applies_keccak_commit<F: RichField + Extendable<D>, C: GenericConfig<D, F
         && type_name::<C::Hasher>() == type_name::<KeccakHash<25>>()
         && core::mem::size_of::<F>() == 8
         && core::mem::size_of::<<C::Hasher as Hasher<F>>::Hash>() == 25
+}
+
+/// Does the GPU FRI (`prove_openings`, `fri_committed_trees`) apply?  Both configs: the transcript's hasher selects the library's
+/// challenger (`challenger_to_device`), and with it the round trees and the grind.
+pub fn applies_fri<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>() -> bool {
+    applies::<F, C, D>(false) || applies_keccak_commit::<F, C, D>()
+}
+
+/// A digest as the library hands it over -- a 32-byte slot of 4 words -- as `H::Hash`: a HashOut is the four words; a
+/// BytesHash<N> is bytes 0..N of the slot (the rest is zero)
+fn hash_from_slot<F: RichField, H: Hasher<F>>(w: &[u64]) -> H::Hash {
+    let mut b = [0u8; 32];
+    for (i, x) in w[..4].iter().enumerate() {
+        b[8 * i..8 * i + 8].copy_from_slice(&x.to_le_bytes());
+    }
+    H::Hash::from_bytes(&b[..core::mem::size_of::<H::Hash>()])
 }
 
 #[inline]
@@ -775,8 +794,9 @@ pub(crate) fn commit_with_salts<F: RichField + Extendable<D>, C: GenericConfig<D
 }
 
 /// `commit` for KeccakGoldilocksConfig (`applies_keccak_commit`): the library builds the KeccakHash<25> tree, whose digests come
-/// back in 32-byte slots (bytes 0..25, the rest zero) and are compacted into `BytesHash<25>` here.  The batch is an ordinary
-/// host-side one -- `leaves`, `digests` and `cap` filled, no `device` handle -- because the CPU `prove_openings` consumes it.
+/// back in 32-byte slots (bytes 0..25, the rest zero) and are compacted into `BytesHash<25>` here.  `leaves`, `digests` and `cap`
+/// are filled on the host -- `MerkleTree::get` / `prove` and the CPU bodies of the quotient read the fields -- and the batch keeps
+/// its `device` handle (coefficients, LDE matrix and digest slots on the GPU) for `prove_openings`.
 pub fn commit_keccak<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>(
     cols: &[&[F]],
     rate_bits: usize,
@@ -800,31 +820,36 @@ pub fn commit_keccak<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, c
     let mut flat = Out::<F>::new(big_n * lw, true); // row-major, committed order (MerkleTree::leaves)
     let mut slots = Out::<[u64; 4]>::new(num_digests, true);
     let mut cap_slots = Out::<[u64; 4]>::new(1 << cap_height, true);
+    let mut handle: *mut P2hotBatch = core::ptr::null_mut();
     with_ctx(|ctx| {
         let rc = unsafe {
             p2hot_commit_salted(
                 ctx, ptrs.as_ptr(), w, log_n as c_uint, rate_bits as c_uint, cap_height as c_uint, is_values as c_int,
                 P2HOT_COEFFS_PER_COLUMN | hash_keccak_flag(hash_n), salt_ptrs.as_ptr(), salt_ptrs.len(), coeff_ptrs.as_ptr() as *mut u64,
-                flat.ptr(), slots.ptr(), cap_slots.ptr(), core::ptr::null_mut(),
+                flat.ptr(), slots.ptr(), cap_slots.ptr(), &mut handle,
             )
         };
         check(ctx, rc, "p2hot_commit_salted (KeccakHash)");
     });
     let (flat, slots, cap_slots) = unsafe { (flat.finish(), slots.finish(), cap_slots.finish()) };
     let polynomials = coeff_vecs.into_iter().map(|o| PolynomialCoeffs::new(unsafe { o.finish() })).collect();
-    let compact = |s: &[u64; 4]| {
-        let mut b = [0u8; 32];
-        for (i, x) in s.iter().enumerate() {
-            b[8 * i..8 * i + 8].copy_from_slice(&x.to_le_bytes());
-        }
-        <C::Hasher as Hasher<F>>::Hash::from_bytes(&b[..hash_n])
-    };
+    let compact = |s: &[u64; 4]| hash_from_slot::<F, C::Hasher>(s);
     let digests: Vec<_> = slots.par_iter().map(compact).collect();
     let cap: Vec<_> = cap_slots.iter().map(compact).collect();
     let leaves: Vec<Vec<F>> = flat.par_chunks_exact(lw).map(|r| r.to_vec()).collect();
+    // the handle only: the host fields above are complete, so `get` / `prove` / `num_leaves` never go through it
+    let device = std::sync::Arc::new(DeviceTree {
+        batch: handle,
+        width: lw,
+        num_leaves: big_n,
+        num_layers: log_n + rate_bits - cap_height,
+        flat: FlatLeaves::Heap(Vec::new()),
+        landed: AtomicUsize::new(big_n),
+        rows: Mutex::new(HashMap::new()),
+    });
     PolynomialBatch {
         polynomials,
-        merkle_tree: MerkleTree { leaves, digests, cap: MerkleCap(cap), device: None },
+        merkle_tree: MerkleTree { leaves, digests, cap: MerkleCap(cap), device: Some(device) },
         degree_log: log_n,
         rate_bits,
         blinding,
@@ -856,7 +881,14 @@ fn challenger_to_device<F: RichField, H: Hasher<F>>(ctx: *mut P2hotCtx, ch: &mut
     st.input_len = input.len() as u32;
     st.output_len = output.len() as u32;
     let mut h: *mut P2hotChallenger = core::ptr::null_mut();
-    check(ctx, unsafe { p2hot_challenger_create(ctx, &mut h) }, "p2hot_challenger_create");
+    // Challenger<F, KeccakHash<N>> (KeccakGoldilocksConfig: N = 25, reached through `applies_fri`) is the library's Keccak
+    // challenger: same state layout, the duplex runs KeccakPermutation, and the handle selects the Keccak FRI trees and grind
+    if type_name::<H>().contains("KeccakHash") {
+        let hash_n = core::mem::size_of::<<H as Hasher<F>>::Hash>() as c_uint;
+        check(ctx, unsafe { p2hot_challenger_create_keccak(ctx, hash_n, &mut h) }, "p2hot_challenger_create_keccak");
+    } else {
+        check(ctx, unsafe { p2hot_challenger_create(ctx, &mut h) }, "p2hot_challenger_create");
+    }
     check(ctx, unsafe { p2hot_challenger_load(h, &st) }, "p2hot_challenger_load");
     DeviceChallenger(h)
 }
@@ -914,8 +946,13 @@ pub fn fri_committed_trees<F: RichField + Extendable<D>, C: GenericConfig<D, F =
     let digest_count: usize = shapes.iter().map(|s| s.2).sum();
     let cap_len = 1usize << cap_height;
     let mut leaves_flat = Out::<F>::new(leaf_words, true);
-    let mut digests_flat = Out::<<C::Hasher as Hasher<F>>::Hash>::new(digest_count, true);
-    let mut caps_flat = Out::<<C::Hasher as Hasher<F>>::Hash>::new(cap_len * shapes.len(), true);
+    // digests and caps arrive as 32-byte slots: a HashOut IS its slot (filled in place); a BytesHash<N> is compacted out of a
+    // slot buffer afterwards (`hash_from_slot`)
+    let in_place = core::mem::size_of::<<C::Hasher as Hasher<F>>::Hash>() == 32;
+    let mut digests_flat = Out::<<C::Hasher as Hasher<F>>::Hash>::new(digest_count, in_place);
+    let mut caps_flat = Out::<<C::Hasher as Hasher<F>>::Hash>::new(cap_len * shapes.len(), in_place);
+    let mut digest_slots = Out::<[u64; 4]>::new(digest_count, !in_place);
+    let mut cap_slots = Out::<[u64; 4]>::new(cap_len * shapes.len(), !in_place);
     let mut final_coeffs = Out::<F::Extension>::new(n_final, true);
     with_ctx(|ctx| {
         let dev = challenger_to_device(ctx, challenger);
@@ -923,14 +960,20 @@ pub fn fri_committed_trees<F: RichField + Extendable<D>, C: GenericConfig<D, F =
             p2hot_fri_commit(
                 ctx, coeffs.coeffs.as_ptr() as *const u64, log2_strict(n.max(1)) as c_uint, rate_bits as c_uint, cap_height as c_uint,
                 arity.as_ptr(), arity.len() as c_uint, max_num_query_steps.unwrap_or(0) as c_uint, final_poly_coeff_len.unwrap_or(0), dev.0,
-                leaves_flat.ptr(), digests_flat.ptr(), caps_flat.ptr(), core::ptr::null_mut(), final_coeffs.ptr(),
+                leaves_flat.ptr(), if in_place { digests_flat.ptr() } else { digest_slots.ptr() },
+                if in_place { caps_flat.ptr() } else { cap_slots.ptr() }, core::ptr::null_mut(), final_coeffs.ptr(),
             )
         };
         check(ctx, rc, "p2hot_fri_commit");
         challenger_from_device(ctx, &dev, challenger);
     });
-    let (leaves_flat, digests_flat, caps_flat, final_coeffs) =
+    let (leaves_flat, mut digests_flat, mut caps_flat, final_coeffs) =
         unsafe { (leaves_flat.finish(), digests_flat.finish(), caps_flat.finish(), final_coeffs.finish()) };
+    if !in_place {
+        let (digest_slots, cap_slots) = unsafe { (digest_slots.finish(), cap_slots.finish()) };
+        digests_flat = digest_slots.par_iter().map(|s| hash_from_slot::<F, C::Hasher>(s)).collect();
+        caps_flat = cap_slots.iter().map(|s| hash_from_slot::<F, C::Hasher>(s)).collect();
+    }
     let mut trees = Vec::with_capacity(shapes.len());
     let (mut lo, mut dg) = (0usize, 0usize);
     for (i, &(n_leaves, width, nd)) in shapes.iter().enumerate() {
@@ -961,7 +1004,7 @@ pub fn prove_openings<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, 
 ) -> Option<FriProof<F, C::Hasher, D>> {
     // FriParams::hiding does not reach the prover's FRI path (it is observed into the transcript by the caller and tells the
     // VERIFIER to strip the salts, fri/verifier.rs:149-151): blinded oracles simply have wider leaves
-    if !applies::<F, C, D>(false) {
+    if !applies_fri::<F, C, D>() {
         return None;
     }
     let handles: Option<Vec<*const P2hotBatch>> = oracles.iter().map(|o| o.merkle_tree.device.as_ref().map(|d| d.raw())).collect();
@@ -1011,7 +1054,7 @@ pub fn prove_openings<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, 
     });
     // flat buffers -> FriProof (layout: include/p2hot.h, p2hot_fri_proof)
     let f = |x: u64| F::from_canonical_u64(x);
-    let hash = |w: &[u64]| -> <C::Hasher as Hasher<F>>::Hash { vec_from_words::<<C::Hasher as Hasher<F>>::Hash>(1, |p| unsafe { core::ptr::copy_nonoverlapping(w.as_ptr(), p, 4) })[0] };
+    let hash = |w: &[u64]| -> <C::Hasher as Hasher<F>>::Hash { hash_from_slot::<F, C::Hasher>(w) }; // slots: HashOut, or BytesHash<N> in bytes 0..N
     let ext = |w: &[u64]| F::Extension::from_basefield_array({
         let mut a = [F::ZERO; D];
         a[0] = f(w[0]);
@@ -1605,12 +1648,13 @@ mod tests {
         type KC = KeccakGoldilocksConfig;
         type KH = <KC as GenericConfig<D>>::Hasher;
         type KBatch = PolynomialBatch<F, KC, D>;
-        assert!(applies_keccak_commit::<F, KC, D>() && !applies::<F, KC, D>(false));
+        assert!(applies_keccak_commit::<F, KC, D>() && applies_fri::<F, KC, D>() && !applies::<F, KC, D>(false));
         for (w, log_n, rate_bits, cap_height) in [(3usize, 5usize, 2usize, 0usize), (135, 6, 3, 2), (20, 7, 1, 8)] {
             let values: Vec<PolynomialValues<F>> = (0..w).map(|_| PolynomialValues::new(F::rand_vec(1 << log_n))).collect();
             let cpu = on_cpu(|| KBatch::from_values(values.clone(), rate_bits, false, cap_height, &mut TimingTree::default(), None));
             let gpu = KBatch::from_values(values.clone(), rate_bits, false, cap_height, &mut TimingTree::default(), None);
-            assert!(gpu.merkle_tree.device.is_none());
+            assert!(gpu.merkle_tree.device.is_some() && !gpu.merkle_tree.leaves.is_empty() && !gpu.merkle_tree.digests.is_empty());
+            assert_eq!(cpu.merkle_tree.prove(1), gpu.merkle_tree.prove(1), "MerkleTree::prove reads the host digests");
             assert_eq!(cpu.merkle_tree.digests, gpu.merkle_tree.digests, "KeccakHash<25> digests");
             assert_eq!(cpu, gpu);
             let coeffs: Vec<PolynomialCoeffs<F>> = values.into_iter().map(|v| v.ifft()).collect();
@@ -1623,5 +1667,67 @@ mod tests {
         let tree = MerkleTree::<F, KH>::new(gpu.merkle_tree.leaves.clone(), 1);
         assert_eq!(gpu.merkle_tree.leaves[0].len(), 9 + SALT_SIZE);
         assert_eq!((tree.digests, tree.cap), (gpu.merkle_tree.digests.clone(), gpu.merkle_tree.cap.clone()));
+    }
+
+    /// KeccakGoldilocksConfig end to end: the commitments, `prove_openings` (Keccak challenger, round trees, grind and query
+    /// rounds in one library call) against the CPU prover, byte for byte, and the reference verifier accepts the GPU proof
+    #[test]
+    fn keccak_config_proof_matches_the_cpu_prover() -> Result<()> {
+        use crate::plonk::config::KeccakGoldilocksConfig;
+        type KC = KeccakGoldilocksConfig;
+        let config = CircuitConfig::standard_recursion_config();
+        let build = || {
+            let mut builder = CircuitBuilder::<F, D>::new(config.clone());
+            for _ in 0..(1 << 7) + 1 {
+                builder.add_gate(NoopGate, vec![]);
+            }
+            builder.build::<KC>()
+        };
+        let cpu_data = on_cpu(&build);
+        let gpu_data = build();
+        assert_eq!(cpu_data.verifier_only.constants_sigmas_cap, gpu_data.verifier_only.constants_sigmas_cap);
+        assert!(gpu_data.prover_only.constants_sigmas_commitment.merkle_tree.device.is_some(), "the p2hot body did not run");
+        let cpu_proof = on_cpu(|| prove::<F, KC, D>(&cpu_data.prover_only, &cpu_data.common, PartialWitness::new(), &mut TimingTree::default()))?;
+        let gpu_proof = prove::<F, KC, D>(&gpu_data.prover_only, &gpu_data.common, PartialWitness::new(), &mut TimingTree::default())?;
+        let (c, g) = (&cpu_proof.proof.opening_proof, &gpu_proof.proof.opening_proof);
+        assert_eq!(c.commit_phase_merkle_caps, g.commit_phase_merkle_caps, "FRI commit_phase_merkle_caps (BytesHash<25>)");
+        assert_eq!(c.final_poly, g.final_poly, "FRI final_poly");
+        assert_eq!(c.pow_witness, g.pow_witness, "pow_witness (smallest on both sides)");
+        assert_eq!(c.query_round_proofs, g.query_round_proofs, "FRI query rounds");
+        assert_eq!(cpu_proof.to_bytes(), gpu_proof.to_bytes(), "proof.to_bytes()");
+        cpu_data.verify(gpu_proof)
+    }
+
+    /// `fri_committed_trees` for the Keccak config (the starky entry): KeccakHash<25> round trees, final polynomial and the
+    /// transcript afterwards equal the CPU body's
+    #[test]
+    fn keccak_config_fri_commit_phase_matches_the_cpu_prover() {
+        use crate::plonk::config::KeccakGoldilocksConfig;
+        type KC = KeccakGoldilocksConfig;
+        type KH = <KC as GenericConfig<D>>::Hasher;
+        for &(log_n, rate_bits, cap_height, ref arity) in &[(6usize, 3usize, 2usize, vec![2usize, 1]), (5, 1, 3, vec![3]), (6, 3, 0, vec![])] {
+            let n = 1usize << log_n;
+            let mut coeffs = <F as Extendable<D>>::Extension::rand_vec(n);
+            coeffs.resize(n << rate_bits, <F as Extendable<D>>::Extension::ZERO);
+            let coeffs = PolynomialCoeffs::new(coeffs);
+            let fri_params = FriParams {
+                config: FriConfig { rate_bits, cap_height, proof_of_work_bits: 4, reduction_strategy: FriReductionStrategy::Fixed(arity.clone()), num_query_rounds: 5 },
+                hiding: false,
+                degree_bits: log_n,
+                reduction_arity_bits: arity.clone(),
+            };
+            let seed = F::rand_vec(7);
+            let run = || {
+                let mut challenger = Challenger::<F, KH>::new();
+                challenger.observe_elements(&seed);
+                let out = crate::fri::prover::p2hot_fri_committed_trees_for_tests::<F, KC, D>(&coeffs, &mut challenger, &fri_params);
+                (out, challenger.get_n_challenges(9))
+            };
+            let ((cpu_trees, cpu_final), cpu_next) = on_cpu(run);
+            let ((gpu_trees, gpu_final), gpu_next) = run();
+            assert_eq!(cpu_trees, gpu_trees, "round trees (leaves, BytesHash<25> digests, caps)");
+            assert_eq!(cpu_final, gpu_final, "final_poly");
+            assert_eq!(cpu_next, gpu_next, "the transcript after the commit phase");
+        }
     }
 }

@@ -90,6 +90,8 @@ SIGNATURES = {
     "p2hot_commit_dev": (i, [vp, vp, sz, sz, u, u, u, i, sz, sz, vp, sz, vp, sz, vp, vp, vp]),
     "p2hot_commit_keccak_dev": (i, [vp, vp, sz, sz, u, u, u, i, sz, sz, vp, sz, vp, sz, vp, vp, vp, u]),
     "p2hot_challenger_create": (i, [vp, C.POINTER(vp)]),
+    "p2hot_challenger_create_keccak": (i, [vp, u, C.POINTER(vp)]),
+    "p2hot_challenger_observe_digests": (i, [vp, vp, sz]),
     "p2hot_challenger_destroy": (None, [vp]),
     "p2hot_challenger_load": (i, [vp, C.POINTER(ChallengerState)]),
     "p2hot_challenger_store": (i, [vp, C.POINTER(ChallengerState)]),

@@ -15,6 +15,7 @@
 #include "poseidon.hpp"
 #include "poseidon4.hpp"
 #include "poseidon16.hpp"
+#include "keccak.hpp"
 
 namespace fri {
 using gl::u32;
@@ -78,6 +79,69 @@ __global__ void __launch_bounds__(64) challenger_kernel(Challenger *ch, const u6
         ch->n_in = n_in;
         ch->n_out = n_out;
     }
+}
+
+// BytesHash<N>::to_vec (hash/hash_types.rs:184-194): element c of a digest is its bytes [7c, 7c + 7) zero-extended ("chunks of
+// 7 bytes since 8 bytes would allow collisions"): ceil(N / 7) elements, 4 for N = 25 and 5 for N = 32.  slot: the digest's
+// 32-byte slot; bytes N..32 are not trusted to be zero.
+__device__ __forceinline__ unsigned digest_elems(unsigned N) { return (N + 6) / 7; }
+__device__ __forceinline__ u64 digest_element(const u64 *slot, unsigned N, unsigned c) {
+    const unsigned b0 = 7 * c, q = b0 >> 3, sh = 8 * (b0 & 7);
+    u64 v = slot[q] >> sh;
+    if (sh > 8 && q + 1 < 4) v |= slot[q + 1] << (64 - sh);  // the 7 bytes cross into the next word
+    const unsigned nb = N - b0 < 7 ? N - b0 : 7;
+    return v & ((1ull << (8 * nb)) - 1);
+}
+
+// The kernels of the Keccak config's FRI carry the suffix _k256 (Keccak-256): the transcript, the round trees' leaves, the grind.
+//
+// The same transcript for Challenger<F, KeccakHash<N>>: the generic duplex (challenger.rs:129-144) over
+// keccak::keccak_permutation.  One lane: a duplex is a chain of three dependent Keccak-f (no lane of a wave could help the
+// next), so the kernel is launched with ONE thread; the buffers sit in LDS because they are indexed by the running lengths.
+// Every observed element passes through that lane: about 37 us per 8 elements on the MI355X (profiles/keccak_fri.json), so a
+// long observation -- a final polynomial of 2^16 coefficients after few reduction rounds -- is a single-thread kernel of 0.6 s.
+// digest_n != 0: obs holds digest slots and the n_obs observed elements are the to_vec elements of those BytesHash<digest_n>
+// (observe_hash / observe_cap, challenger.rs:69-80), element e = chunk e % per of slot e / per.
+__global__ void __launch_bounds__(1) challenger_kernel_k256(Challenger *ch, const u64 *obs, size_t n_obs, u64 *out,
+                                                              size_t n_get, unsigned digest_n) {
+    __shared__ u64 inbuf[8];
+    __shared__ u64 outbuf[8];
+    u32 n_in = ch->n_in, n_out = ch->n_out;
+    u64 st[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) st[i] = ch->state[i];
+    for (int i = 0; i < 8; ++i) {
+        inbuf[i] = ch->in[i];
+        outbuf[i] = ch->out[i];
+    }
+    auto duplex = [&]() {
+#pragma unroll
+        for (unsigned i = 0; i < 8; ++i)
+            if (i < n_in) st[i] = inbuf[i];
+        keccak::keccak_permutation(st);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) outbuf[i] = st[i];
+        n_in = 0;
+        n_out = 8;
+    };
+    const unsigned per = digest_n ? digest_elems(digest_n) : 1;
+    for (size_t i = 0; i < n_obs; ++i) {
+        n_out = 0;
+        inbuf[n_in] = digest_n ? digest_element(obs + 4 * (i / per), digest_n, (unsigned)(i % per)) : gl::canon(obs[i]);
+        if (++n_in == 8) duplex();
+    }
+    for (size_t i = 0; i < n_get; ++i) {
+        if (n_in != 0 || n_out == 0) duplex();
+        out[i] = outbuf[--n_out];
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ch->state[i] = st[i];
+    for (int i = 0; i < 8; ++i) {
+        ch->in[i] = inbuf[i];
+        ch->out[i] = outbuf[i];
+    }
+    ch->n_in = n_in;
+    ch->n_out = n_out;
 }
 
 // coeffs'[j] = sum_{i < arity} beta^i * coeffs[arity*j + i]  (Horner from the top, plonk_common.rs:120-132)
@@ -472,6 +536,41 @@ __global__ void __launch_bounds__(256) pow_kernel(const Challenger *ch, unsigned
         if ((u32)i == n_in) s[i] = cand;
     poseidon::permute(s);
     u64 resp = gl::canon(s[7]);
+    unsigned lz = resp ? (unsigned)__clzll((long long)resp) : 64u;
+    if (lz >= pow_bits) atomicMin(best, (unsigned long long)cand);
+}
+
+// The leaves of a round tree under KeccakHash<N> (fri/prover.rs:99-104): hash_or_noop of 2 << arity_bits words each, which
+// copies the leaf when 8 * W <= N (N = 32 at arity 2) -- the commitments' leaf sponge over the planar FRI layout
+__global__ void __launch_bounds__(256) round_leaves_kernel_k256(merkle::FriPlanarReader rd, unsigned W, size_t leaf_offset,
+                                                               size_t leaf_count, unsigned h, unsigned N, u64 *digests, u64 *cap) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= leaf_count) return;
+    const size_t L = leaf_offset + t;
+    keccak::leaf_digest(rd, W, L, N, merkle::node_slot(digests, cap, h, 0, L));
+}
+
+// The grind for Challenger<F, KeccakHash<N>> (fri/prover.rs:179-195): the same duplex intermediate state with the candidate
+// at the next input slot, through keccak::keccak_permutation (three Keccak-f per candidate, more after a rejected word);
+// the response is kept word 7.  One candidate per lane.
+__global__ void __launch_bounds__(256) pow_kernel_k256(const Challenger *ch, unsigned pow_bits, u64 start, u64 count,
+                                                        unsigned long long *best) {
+    u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    if (*best < (unsigned long long)start) return;  // see pow_kernel
+    // the duplex intermediate state: the sponge state, its first n_in words overwritten by the buffered inputs, the candidate next
+    u64 s[12];
+    const u32 n_in = ch->n_in;
+    const u64 cand = start + t;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = ch->state[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if ((u32)i < n_in) s[i] = ch->in[i];
+        if ((u32)i == n_in) s[i] = cand;
+    }
+    keccak::keccak_permutation(s);
+    const u64 resp = s[7];  // canonical: only words < p are kept
     unsigned lz = resp ? (unsigned)__clzll((long long)resp) : 64u;
     if (lz >= pow_bits) atomicMin(best, (unsigned long long)cand);
 }

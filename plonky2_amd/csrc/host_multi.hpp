@@ -1069,6 +1069,9 @@ extern "C" int p2hot_group_prove_openings(p2hot_group *g, const p2hot_fri_batch_
     unsigned log_n = 0;
     {
         P2_ENTER(ctx);
+        if (challenger && challenger->hash_n)  // sharded commitments are Poseidon trees
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "group_prove_openings: the challenger is a KeccakHash<%u> transcript (sharded commitments are Poseidon trees)",
+                    challenger->hash_n);
         P2_TRY(sharded_views(g, oracles, n_oracles, &views, &log_n));
         for (size_t o = 0; o < n_oracles && fp; ++o)
             if (oracles[o]->plan.rate_bits != fp->rate_bits || oracles[o]->plan.cap_height != fp->cap_height)

@@ -959,9 +959,17 @@ extern "C" int p2hot_prove_openings(p2hot_ctx *ctx, const p2hot_fri_batch_info *
     std::vector<OracleView> views;
     for (size_t o = 0; o < n_oracles; ++o) {
         if (!oracles[o] || oracles[o]->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: oracle %zu is null or belongs to another context", o);
-        if (oracles[o]->hash_n)
-            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings: oracle %zu is a KeccakHash<%u> tree (FRI for the Keccak config runs on the CPU)", o,
-                    oracles[o]->hash_n);
+        // Challenger<F, C::Hasher> (fri/oracle.rs:180): one hasher for the transcript and every tree.  Refused before any HIP call.
+        if (challenger && oracles[o]->hash_n != challenger->hash_n) {
+            if (!challenger->hash_n)
+                P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings: oracle %zu is a KeccakHash<%u> tree and the challenger a Poseidon one (create it with "
+                        "p2hot_challenger_create_keccak)", o, oracles[o]->hash_n);
+            if (!oracles[o]->hash_n)
+                P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings: oracle %zu is a Poseidon tree and the challenger a KeccakHash<%u> one", o,
+                        challenger->hash_n);
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings: oracle %zu is a KeccakHash<%u> tree and the challenger a KeccakHash<%u> one", o,
+                    oracles[o]->hash_n, challenger->hash_n);
+        }
         if (oracles[o]->log_n != oracles[0]->log_n || (fp && (oracles[o]->rate_bits != fp->rate_bits || oracles[o]->cap_height != fp->cap_height)))
             P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: oracle %zu was committed with another degree / rate / cap height", o);
         views.push_back(OracleView{oracles[o]->d_coef, oracles[o]->d_lde, oracles[o]->d_dig, oracles[o]->W, oracles[o]->N, oracles[o]->S,
@@ -1022,11 +1030,14 @@ extern "C" int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_f
     std::vector<std::vector<OracleView>> views(M);
     for (size_t j = 0; j < M; ++j) {
         if (!challengers[j] || challengers[j]->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings_many: challenger %zu is null or belongs to another context", j);
+        if (challengers[j]->hash_n)  // (the helper contexts carry Poseidon transcripts)
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings_many: challenger %zu is a KeccakHash<%u> transcript (Keccak opening proofs: p2hot_prove_openings, one at a time)",
+                    j, challengers[j]->hash_n);
         for (size_t o = 0; o < n_oracles; ++o) {
             const p2hot_batch *B = oracles[j * n_oracles + o];
             if (!B || B->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings_many: oracle %zu of proof %zu is null or belongs to another context", o, j);
             if (B->hash_n)
-                P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings_many: oracle %zu of proof %zu is a KeccakHash<%u> tree (FRI for the Keccak config runs on the CPU)",
+                P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "prove_openings_many: oracle %zu of proof %zu is a KeccakHash<%u> tree (Keccak opening proofs: p2hot_prove_openings, one at a time)",
                         o, j, B->hash_n);
             if (B->log_n != oracles[0]->log_n || (fp && (B->rate_bits != fp->rate_bits || B->cap_height != fp->cap_height)))
                 P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings_many: oracle %zu of proof %zu was committed with another degree / rate / cap height", o, j);

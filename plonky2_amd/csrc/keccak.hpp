@@ -21,6 +21,8 @@ using gl::u64;
 // plain-C stand-ins for the emulator build: a generic truth-table evaluator and the 64-bit funnel shift
 template <unsigned IMM>
 static inline u32 bitop3(u32 a, u32 b, u32 c) {
+    if (IMM == 0x96) return a ^ b ^ c;     // the two tables Keccak-f uses, word-wide (the grind emulates 2^14 candidates a launch)
+    if (IMM == 0xD2) return a ^ (~b & c);
     u32 r = 0;
     for (unsigned i = 0; i < 32; ++i) {
         const unsigned idx = (((a >> i) & 1u) << 2) | (((b >> i) & 1u) << 1) | ((c >> i) & 1u);
@@ -111,15 +113,39 @@ __device__ __forceinline__ void store_digest(u64 *dst, const u64 s[25], unsigned
     }
 }
 
+// KeccakPermutation::permute (hash/keccak.rs:63-94) on the 12 words of a sponge state, in place: h_1 = Keccak-256 of the 96
+// canonical little-endian bytes (one block: 12 words, the domain byte in word 12), h_{k+1} = Keccak-256(h_k) (32 bytes, one
+// block); the hashes are read as 4 little-endian words each and every word >= p is DROPPED (rejection sampling, not reduction:
+// about one word in 2^32) until 12 words are kept -- three hashes, or more after a rejection.  The kept-word count differs
+// between lanes only then, so st[] is written by compare-and-select on constant indices: the state stays in registers.
+__device__ __forceinline__ void keccak_permutation(u64 st[12]) {
+    u64 s[25];
+#pragma unroll
+    for (int i = 0; i < 25; ++i) s[i] = i < 12 ? gl::canon(st[i]) : 0;
+    pad_words(s, 12, 0x01);
+    unsigned kept = 0;
+    do {
+        keccak_f(s);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const u64 w = s[i];
+            const bool keep = w < gl::P && kept < 12;
+#pragma unroll
+            for (unsigned j = 0; j < 12; ++j)
+                if (keep && j == kept) st[j] = w;
+            kept += keep ? 1u : 0u;
+        }
+        // the next message is this hash: words 0..3 stay, the domain byte follows them
+#pragma unroll
+        for (int i = 4; i < 25; ++i) s[i] = 0;
+        pad_words(s, 4, 0x01);
+    } while (kept < 12);
+}
+
 // hash_or_noop of every leaf (plonk/config.rs:63-74) for KeccakHash<N>: a leaf of 8W <= N bytes is its canonical bytes
 // zero-padded, any other is Keccak-256 of its 8W canonical bytes truncated to N; digest -> level-0 slot
 template <class Reader>
-__global__ void __launch_bounds__(256) keccak_leaves_kernel(Reader rd, unsigned W, size_t leaf_offset, size_t leaf_count,
-                                                           unsigned h, unsigned N, u64 *digests, u64 *cap) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= leaf_count) return;
-    const size_t L = leaf_offset + t;
-    u64 *dst = merkle::node_slot(digests, cap, h, 0, L);
+__device__ __forceinline__ void leaf_digest(const Reader &rd, unsigned W, size_t L, unsigned N, u64 *dst) {
     if (8 * W <= N) {  // no hash (W <= 4)
 #pragma unroll
         for (unsigned i = 0; i < 4; ++i) dst[i] = i < W ? gl::canon(rd(L, i)) : 0;
@@ -141,6 +167,15 @@ __global__ void __launch_bounds__(256) keccak_leaves_kernel(Reader rd, unsigned 
     pad_words(s, rem, 0x01);
     keccak_f(s);
     store_digest(dst, s, N);
+}
+
+template <class Reader>
+__global__ void __launch_bounds__(256) keccak_leaves_kernel(Reader rd, unsigned W, size_t leaf_offset, size_t leaf_count,
+                                                           unsigned h, unsigned N, u64 *digests, u64 *cap) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= leaf_count) return;
+    const size_t L = leaf_offset + t;
+    leaf_digest(rd, W, L, N, merkle::node_slot(digests, cap, h, 0, L));
 }
 
 // one tree level: node j = Keccak-256(left[0..N] || right[0..N]) truncated (keccak.rs:118-127, merkle_tree.rs:108-112).  The

@@ -1206,8 +1206,9 @@ static int hash_leaves_range(p2hot_ctx *ctx, hipStream_t stream, Reader rd, size
     if (count == 0) return P2HOT_OK;
     ProfScope ps(ctx, "hash_leaves", stream, true);
     if (hash_n) {
-        if constexpr (std::is_same<Reader, merkle::FriPlanarReader>::value) {  // FRI trees stay Poseidon (no Keccak FRI)
-            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "hash_leaves: Keccak FRI trees");
+        if constexpr (std::is_same<Reader, merkle::FriPlanarReader>::value) {  // the round trees of a Keccak challenger's commit phase
+            P2HOT_LAUNCH(fri::round_leaves_kernel_k256, dim3(cdiv(count, 256)), dim3(256), 0, stream, rd, (unsigned)W, leaf_offset, count,
+                         g.h, hash_n, g.dig, g.cap);
         } else {
             P2HOT_LAUNCH((keccak::keccak_leaves_kernel<Reader>), dim3(cdiv(count, 256)), dim3(256), 0, stream, rd, (unsigned)W,
                          leaf_offset, count, g.h, hash_n, g.dig, g.cap);
@@ -1449,6 +1450,7 @@ struct p2hot_challenger {
     fri::Challenger *d;
     u64 *d_io;  // small staging buffer
     size_t io_cap;
+    unsigned hash_n = 0;  // the transcript's hasher: 0 = Challenger<F, PoseidonHash>, 1..32 = Challenger<F, KeccakHash<hash_n>>
 };
 
 static int challenger_io(p2hot_challenger *ch, size_t words, u64 **out) {
@@ -1468,10 +1470,9 @@ static int challenger_io(p2hot_challenger *ch, size_t words, u64 **out) {
     return P2HOT_OK;
 }
 
-extern "C" int p2hot_challenger_create(p2hot_ctx *ctx, p2hot_challenger **out) {
-    if (!ctx || !out) return P2HOT_EINVAL;
+static int challenger_create(p2hot_ctx *ctx, unsigned hash_n, p2hot_challenger **out) {
     DeviceGuard dev_guard_(ctx);
-    p2hot_challenger *ch = new p2hot_challenger{ctx, nullptr, nullptr, 0};
+    p2hot_challenger *ch = new p2hot_challenger{ctx, nullptr, nullptr, 0, hash_n};
     hipError_t e = hipMalloc((void **)&ch->d, sizeof(fri::Challenger));
     if (e != hipSuccess) {
         delete ch;
@@ -1485,6 +1486,17 @@ extern "C" int p2hot_challenger_create(p2hot_ctx *ctx, p2hot_challenger **out) {
     }
     *out = ch;
     return P2HOT_OK;
+}
+
+extern "C" int p2hot_challenger_create(p2hot_ctx *ctx, p2hot_challenger **out) {
+    if (!ctx || !out) return P2HOT_EINVAL;
+    return challenger_create(ctx, 0, out);
+}
+
+extern "C" int p2hot_challenger_create_keccak(p2hot_ctx *ctx, unsigned hash_size, p2hot_challenger **out) {
+    if (!ctx || !out) return P2HOT_EINVAL;
+    P2_TRY(check_hash_size(ctx, hash_size, "challenger_create_keccak"));
+    return challenger_create(ctx, hash_size, out);
 }
 
 extern "C" void p2hot_challenger_destroy(p2hot_challenger *ch) {
@@ -1521,8 +1533,37 @@ extern "C" int p2hot_challenger_store(p2hot_challenger *ch, p2hot_challenger_sta
 static int challenger_step_dev(p2hot_challenger *ch, const u64 *d_obs, size_t n_obs, u64 *d_out, size_t n_get) {
     p2hot_ctx *ctx = ch->ctx;
     if (n_obs == 0 && n_get == 0) return P2HOT_OK;
-    P2HOT_LAUNCH(fri::challenger_kernel, dim3(1), dim3(64), 0, ctx->stream, ch->d, d_obs, n_obs, d_out, n_get);
+    if (ch->hash_n)
+        P2HOT_LAUNCH(fri::challenger_kernel_k256, dim3(1), dim3(1), 0, ctx->stream, ch->d, d_obs, n_obs, d_out, n_get, 0u);
+    else
+        P2HOT_LAUNCH(fri::challenger_kernel, dim3(1), dim3(64), 0, ctx->stream, ch->d, d_obs, n_obs, d_out, n_get);
     P2_LAUNCH_CHECK(ctx);
+    return P2HOT_OK;
+}
+
+// observe_cap / observe_hash (challenger.rs:69-80) of `count` digests in their slots on the device, then squeeze n_get
+// challenges: a HashOut is its 4 words; a BytesHash<N> its ceil(N / 7) seven-byte chunks (fri::digest_element)
+static int challenger_observe_digests_dev(p2hot_challenger *ch, const u64 *d_slots, size_t count, u64 *d_out, size_t n_get) {
+    p2hot_ctx *ctx = ch->ctx;
+    if (!ch->hash_n) return challenger_step_dev(ch, d_slots, 4 * count, d_out, n_get);
+    if (count == 0 && n_get == 0) return P2HOT_OK;
+    P2HOT_LAUNCH(fri::challenger_kernel_k256, dim3(1), dim3(1), 0, ctx->stream, ch->d, d_slots, count * ((ch->hash_n + 6) / 7), d_out,
+                 n_get, ch->hash_n);
+    P2_LAUNCH_CHECK(ctx);
+    return P2HOT_OK;
+}
+
+extern "C" int p2hot_challenger_observe_digests(p2hot_challenger *ch, const uint64_t *slots, size_t count) {
+    if (!ch) return P2HOT_EINVAL;
+    p2hot_ctx *ctx = ch->ctx;
+    DeviceGuard dev_guard_(ctx);
+    if (count && !slots) P2_FAIL(ctx, P2HOT_EINVAL, "challenger: null buffer");
+    if (count == 0) return P2HOT_OK;
+    u64 *io;
+    P2_TRY(challenger_io(ch, 4 * count, &io));
+    P2_HIP(ctx, hipMemcpyAsync(io, slots, count * 32, hipMemcpyHostToDevice, ctx->stream));
+    P2_TRY(challenger_observe_digests_dev(ch, io, count, nullptr, 0));
+    P2_HIP(ctx, stream_sync(ctx));
     return P2HOT_OK;
 }
 
@@ -1619,7 +1660,7 @@ static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_
             const unsigned log_leaves = log_cur + rate_bits - ab;
             const size_t n_leaves = (size_t)1 << log_leaves;
             P2_TRY(merkle_forest(ctx, merkle::FriPlanarReader{v0, v1, ab}, (size_t)2 << ab, log_leaves, cap_height, 0,
-                                 n_leaves, digests.u(), cap.u()));
+                                 n_leaves, digests.u(), cap.u(), challenger->hash_n));
             const size_t nd = p2hot_num_digests(log_leaves, cap_height);
             if (digests_out) {
                 if (nd)
@@ -1633,7 +1674,7 @@ static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_
                 caps_out += cap_words;
             }
             // prover.rs:106-109: observe_cap, beta = get_extension_challenge (stays on the device)
-            P2_TRY(challenger_step_dev(challenger, cap.u(), cap_words, beta.u(), 2));
+            P2_TRY(challenger_observe_digests_dev(challenger, cap.u(), (size_t)1 << cap_height, beta.u(), 2));
             if (betas_out) {
                 P2_TRY(d2h(ctx, betas_out, beta.p, 16));
                 betas_out += 2;
@@ -1652,7 +1693,8 @@ static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_
             shift = gl::pow(shift, (u64)1 << ab);
         }
         // prover.rs:122-132: keep the transcript in sync with a verifier circuit that has more query steps:
-        // observe an all-zero cap and draw a dummy challenge per missing step
+        // observe an all-zero cap and draw a dummy challenge per missing step.  The reference observes NUM_HASH_OUT_ELTS = 4 zero
+        // ELEMENTS per cap entry whatever the hasher (:126-129) -- not what a real BytesHash<N> cap with N > 28 observes
         if (max_num_query_steps > n_rounds) {
             P2_HIP(ctx, hipMemsetAsync(cap.p, 0, cap_words * 8, ctx->stream));
             for (unsigned k = n_rounds; k < max_num_query_steps; ++k)
@@ -1924,6 +1966,17 @@ extern "C" int p2hot_merkle_paths_dev(p2hot_ctx *ctx, const uint64_t *d_digests,
     return P2HOT_OK;
 }
 
+// candidates [start, start + count) through the transcript's permutation
+static int pow_launch(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bits, u64 start, u64 count, unsigned long long *d_best) {
+    if (challenger->hash_n)
+        P2HOT_LAUNCH(fri::pow_kernel_k256, dim3(cdiv(count, 256)), dim3(256), 0, ctx->stream, challenger->d, pow_bits, start, count,
+                     d_best);
+    else
+        P2HOT_LAUNCH(fri::pow_kernel, dim3(cdiv(count, 256)), dim3(256), 0, ctx->stream, challenger->d, pow_bits, start, count, d_best);
+    P2_LAUNCH_CHECK(ctx);
+    return P2HOT_OK;
+}
+
 // fri_proof_of_work (fri/prover.rs:153-202) without a host round trip: chunks of candidates (doubling from 2^14) are
 // enqueued back to back up to 2^(pow_bits + 5) candidates; a chunk retires at once when an earlier one has found a
 // witness.  d_best (8 bytes, device) receives the SMALLEST witness, or stays ~0 if none was found in that range
@@ -1943,8 +1996,7 @@ static int pow_search_dev(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned
     u64 chunk = (u64)1 << std::min(18u, std::max(14u, pow_bits)), start = 0;
     while (start < limit) {
         const u64 count = std::min(limit - start, chunk);
-        P2HOT_LAUNCH(fri::pow_kernel, dim3(cdiv(count, 256)), dim3(256), 0, ctx->stream, challenger->d, pow_bits, start, count, d_best);
-        P2_LAUNCH_CHECK(ctx);
+        P2_TRY(pow_launch(ctx, challenger, pow_bits, start, count, d_best));
         start += count;
         if (chunk < ((u64)1 << 24)) chunk <<= 1;
     }
@@ -1960,8 +2012,7 @@ static int pow_continue_host(p2hot_ctx *ctx, p2hot_challenger *challenger, unsig
     while (start < gl::P) {  // candidates 0 ..= P-1 in the reference (prover.rs:182)
         const u64 count = std::min(gl::P - start, chunk);
         if (chunk < ((u64)1 << 24)) chunk <<= 1;
-        P2HOT_LAUNCH(fri::pow_kernel, dim3(cdiv(count, 256)), dim3(256), 0, ctx->stream, challenger->d, pow_bits, start, count, d_best);
-        P2_LAUNCH_CHECK(ctx);
+        P2_TRY(pow_launch(ctx, challenger, pow_bits, start, count, d_best));
         P2_HIP(ctx, hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
         P2_HIP(ctx, stream_sync(ctx));
         if (best != ~0ull) break;

@@ -106,7 +106,7 @@ class PolynomialBatch:
         blinding=True: `salts` = the SALT_SIZE random vectors [4][N] the reference draws with F::rand_vec (oracle.rs:133-137);
         the caller owns the randomness.
         hasher: None = PoseidonHash; hash.keccak.KeccakHash(N) builds the tree with KeccakHash<N> (host columns only: the
-        batch records its hasher, and prove_openings refuses it)."""
+        batch records its hasher, and prove_openings opens it with a Challenger of the same KeccakHash)."""
         return cls._build(values, rate_bits, blinding, cap_height, True, engine, keep_values, salts, hasher)
 
     @classmethod
@@ -319,7 +319,8 @@ def final_poly_device(batches, oracles, alpha, engine=None):
 def prove_openings(batches, oracles, challenger, rate_bits, cap_height, reduction_arity_bits, proof_of_work_bits,
                    num_query_rounds, engine=None, timing=None, final_poly_coeff_len=None, max_num_query_steps=None):
     """PolynomialBatch::prove_openings + fri_proof (oracle.rs:176-237, fri/prover.rs:24-82): one p2hot_prove_openings
-    call.  Returns a dict shaped like FriProof:
+    call.  The challenger and every oracle share one hasher (Poseidon, or the same KeccakHash(N): digests then are the 32-byte
+    slots); a mixture raises EUNSUPPORTED.  Returns a dict shaped like FriProof:
       commit_phase_merkle_caps, query_round_proofs [{initial_trees_proof: [(leaf, siblings)...], steps: [(evals, siblings)...]}],
       final_poly [[c0, c1]...], pow_witness.
     `timing` (a dict): total synchronised wall milliseconds of the call under "prove_openings"."""

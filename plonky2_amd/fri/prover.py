@@ -16,8 +16,8 @@ def fri_committed_trees(coeffs, challenger, rate_bits, cap_height, reduction_ari
     coeffs: [n][2] uint64 -- the nonzero extension coefficients of final_poly (the reference passes
     them zero-padded to N = n << rate_bits together with their coset-FFT `values`; both are implicit
     here: the LDE runs on the GPU).  challenger: plonky2_amd.iop.challenger.Challenger, advanced
-    like the reference.  Returns (trees, final_coeffs, betas): trees are MerkleTree objects whose
-    leaves are rows of 2*arity words.
+    like the reference; a Challenger(hasher=KeccakHash(N)) builds KeccakHash<N> round trees (digests in 32-byte
+    slots).  Returns (trees, final_coeffs, betas): trees are MerkleTree objects whose leaves are rows of 2*arity words.
     """
     eng = engine or challenger.engine or default_engine()
     coeffs = np.ascontiguousarray(np.asarray(coeffs, dtype=np.uint64))
@@ -73,6 +73,7 @@ def _commit(coeffs, planes, log_n, challenger, rate_bits, cap_height, reduction_
                               cap=caps[4 * ncap * i:4 * ncap * (i + 1)].reshape(ncap, 4), cap_height=cap_height, n_leaves=nl,
                               leaf_getter=(lambda idx, lv=lv: eng.host(lv[np.asarray(idx, dtype=np.int64)])),
                               engine=eng if nd else None)
+        tree.hasher = getattr(challenger, "hasher", None)  # the round trees are built by the transcript's hasher (C::Hasher)
         trees.append(tree)
         lo += 2 * mi
         do += 4 * nd

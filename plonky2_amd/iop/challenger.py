@@ -13,10 +13,17 @@ from ..engine import default_engine
 
 
 class Challenger:
-    def __init__(self, engine=None):  # Challenger::new, challenger.rs:30-37
+    def __init__(self, engine=None, hasher=None):  # Challenger::<F, H>::new, challenger.rs:30-37
+        """hasher: None = PoseidonHash, or a plonky2_amd.hash.keccak.KeccakHash (the transcript of KeccakGoldilocksConfig)"""
+        from ..hash.keccak import hash_size
         self.engine = engine or default_engine()
+        self.hasher = hasher
+        self._hash_n = hash_size(hasher)
         h = C.c_void_p()
-        self.engine.check(self.engine.lib.p2hot_challenger_create(self.engine.ctx, C.byref(h)))
+        if self._hash_n:
+            self.engine.check(self.engine.lib.p2hot_challenger_create_keccak(self.engine.ctx, self._hash_n, C.byref(h)))
+        else:
+            self.engine.check(self.engine.lib.p2hot_challenger_create(self.engine.ctx, C.byref(h)))
         self._h = h
 
     def __del__(self):
@@ -48,10 +55,28 @@ class Challenger:
     def observe_extension_elements(self, es):
         self._step(np.asarray(es, dtype=np.uint64).reshape(-1), 0)
 
+    def _observe_digests(self, d):
+        """digests of a Keccak transcript: uint8 [count][N] bytes (BytesHash<N>), or their slot words [count][4]"""
+        from ..hash.keccak import from_bytes
+        d = np.asarray(d)
+        if d.dtype == np.uint8:
+            if d.shape[-1] != self._hash_n:
+                raise ValueError("digests of %d bytes for a KeccakHash<%d> challenger" % (d.shape[-1], self._hash_n))
+            slots = from_bytes(d)
+        else:
+            slots = np.asarray(d, dtype=np.uint64).reshape(-1, 4)
+        slots = np.ascontiguousarray(slots)
+        if len(slots):
+            self.engine.check(self.engine.lib.p2hot_challenger_observe_digests(self._h, slots.ctypes.data, len(slots)))
+
     def observe_hash(self, h):
+        if self._hash_n:
+            return self._observe_digests(h)
         self._step(h, 0)
 
     def observe_cap(self, cap):
+        if self._hash_n:
+            return self._observe_digests(cap)
         self._step(np.asarray(cap, dtype=np.uint64).reshape(-1), 0)
 
     # challenger.rs:82-116

@@ -56,7 +56,8 @@ GATE = '''        #[cfg(feature = "p2hot")]
         }
         #[cfg(feature = "p2hot")]
         if crate::p2hot::applies_keccak_commit::<F, C, D>() {
-            // KeccakGoldilocksConfig: the same LDE with a KeccakHash<25> tree; FRI and the rest stay on the CPU bodies
+            // KeccakGoldilocksConfig: the same LDE with a KeccakHash<25> tree; the batch keeps its device handle for the opening
+            // proof (crate::p2hot::prove_openings), the quotient and the partial products stay on the CPU bodies
             return timed!(
                 timing,
                 "p2hot commit (KeccakHash)",
@@ -134,7 +135,8 @@ fn main() {
                 max_num_query_steps
             )
         ) {
-            // alpha, final_poly, its LDE, the commit phase, the grind and the query rounds ran on the GPU
+            // alpha, final_poly, its LDE, the commit phase, the grind and the query rounds ran on the GPU (both configs: the
+            // Keccak one through the library's Keccak challenger)
             return proof;
         }
         let alpha = challenger.get_extension_challenge::<D>();
@@ -220,8 +222,9 @@ fn main() {
 ''', '''    max_num_query_steps: Option<usize>,
 ) -> FriCommitedTrees<F, C, D> {
     #[cfg(feature = "p2hot")]
-    if crate::p2hot::applies::<F, C, D>(false) {
-        // every round (tree, challenge, fold, coset NTT) on the GPU; `values` is recomputed there from `coeffs`
+    if crate::p2hot::applies_fri::<F, C, D>() {
+        // every round (tree, challenge, fold, coset NTT) on the GPU; `values` is recomputed there from `coeffs`.  The transcript's
+        // hasher selects the trees: PoseidonGoldilocksConfig, or KeccakGoldilocksConfig with the library's Keccak challenger
         return crate::p2hot::fri_committed_trees::<F, C, D>(
             &coeffs,
             challenger,
