@@ -279,7 +279,7 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * A context runs ONE host-pointer call at a time; a second thread entering gets P2HOT_EBUSY (plonky2 calls these
  * from the main thread, outside its rayon closures).  Serialised by the library (busy guard): p2hot_commit*, p2hot_cols_upload,
  * p2hot_batch_coeffs / _rows / _paths / _digests / _subgroup_values, p2hot_eval_openings, p2hot_prove_openings, p2hot_partial_products,
- * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_ctx_trim.  p2hot_batch_free / p2hot_cols_free may be called from any thread at any time (a
+ * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_quotient_polys_lookup, p2hot_lookup_polys, p2hot_cols_concat, p2hot_ctx_trim.  p2hot_batch_free / p2hot_cols_free may be called from any thread at any time (a
  * Drop, a finaliser): the block cache has its own lock.  Everything else -- the *_dev building blocks, p2hot_fri_commit,
  * p2hot_fri_pow, p2hot_challenger_* -- enqueues on the context's stream without a guard: the CALLER serialises those with
  * each other and with the host-pointer calls of the same context (the Rust shim holds the context behind a Mutex). */
@@ -524,6 +524,48 @@ int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_b
                          const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
                          unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
                          unsigned num_challenges, const uint64_t *const *gate_sums, uint64_t *values_out, p2hot_cols **chunks_out);
+
+/* ---------------------------------------------------------------- the lookup argument (circuits with lookup tables)
+ * Poseidon configuration, single GPU: a KeccakHash commitment is P2HOT_EUNSUPPORTED, and the multi-GPU group has no lookup entry point.
+ * Slots: num_lu_slots = LookupGate::num_slots = num_routed_wires / 2 (gates/lookup.rs:58-69: looking inp / out on wires 2s, 2s + 1),
+ * num_lut_slots = LookupTableGate::num_slots = num_routed_wires / 3 (gates/lookup_table.rs:64-82: looked inp / out / multiplicity on
+ * wires 3s, 3s + 1, 3s + 2).  deltas HOST [num_challenges][4] = ChallengeA, ChallengeB, ChallengeAlpha, ChallengeDelta
+ * (plonk/circuit_builder.rs:68-73), the order of the prover's `deltas`.
+ *
+ * compute_all_lookup_polys (plonk/prover.rs:451-605): for every challenge RE and the S = ceil(num_lu_slots / lookup_degree) partial
+ * SLDC polynomials as values on the trace subgroup (lookup_degree = max_quotient_degree_factor - 1, prover.rs:470-473); rows outside
+ * every [last_lu_gate, first_lut_gate] are zero.
+ *   wires        columns [wires_first_col, ...) of a device-resident column set: MatrixWitness.wire_values
+ *   lookup_rows  HOST [num_luts][3] = last_lu_gate, last_lut_gate, first_lut_gate (LookupWire), in prover_data.lookup_rows order.  The
+ *                regions are processed in that order, each reading the values at first_lut_gate + 1 as the earlier ones left them
+ *                (prover.rs:517, :528, :561)
+ *   out_host [num_challenges * (S + 1)][n] and / or out_cols: RE, SLDC_0 .. SLDC_{S-1} of challenge 0, then challenge 1, ...
+ * P2HOT_EINVAL: first_lut_gate + 1 >= n (the reference indexes out of bounds), rows not ordered last_lu <= last_lut <= first_lut, slots
+ * beyond the wires given, lookup_degree == 0, num_challenges outside 1..4, and a zero alpha - combination ("Tried to invert zero":
+ * the reference panics in batch_multiplicative_inverse). */
+int p2hot_lookup_polys(p2hot_ctx *ctx, const p2hot_cols *wires, size_t wires_first_col, unsigned num_lu_slots, unsigned num_lut_slots,
+                       unsigned lookup_degree, const uint64_t *lookup_rows, unsigned num_luts, const uint64_t *deltas,
+                       unsigned num_challenges, uint64_t *out_host, p2hot_cols **out_cols);
+/* p2hot_quotient_polys for a circuit with lookup tables: the terms of check_lookup_constraints_batch (plonk/vanishing_poly.rs:515-664)
+ * of challenge 0, 1, ... enter the term list between the partial-product terms and the gate terms (vanishing_poly.rs:317-322):
+ *   value_a(x) = (reduce_with_powers(permutation terms ++ lookup terms, alpha_a) + alpha_a^(K + Klu) * gate_sums[a][i]) / Z_H(x),
+ *   Klu = num_challenges * (4 + num_luts + 2 S),  S = ceil(num_lu_slots / (quotient_degree_factor - 1))
+ * Every argument of p2hot_quotient_polys keeps its meaning, and:
+ *   zs_partial_products_lookups  Z_0 .. Z_{nc-1}, the partial products, then the lookup polynomials in p2hot_lookup_polys' order
+ *                                (prover.rs:237-241): exactly nc (1 + num_prods) + nc (S + 1) polynomials, else P2HOT_EINVAL
+ *   lookup_selectors_first_col   the 4 + num_luts lookup selector columns of constants_sigmas: TransSre, TransLdc, InitSre, LastLdc
+ *                                (gates/selectors.rs:34-78), then one end selector per LUT (:82-99)
+ *   lut_re_poly_evals            HOST [num_challenges][num_luts]: get_lut_poly(..).eval(delta) (prover.rs:652-680), the caller's
+ * 2 num_lu_slots or 3 num_lut_slots beyond the wires commitment, and num_challenges outside 1..4, are P2HOT_EINVAL. */
+int p2hot_quotient_polys_lookup(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                const p2hot_batch *zs_partial_products_lookups, const uint64_t *k_is, unsigned num_routed,
+                                unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                unsigned num_challenges, const uint64_t *const *gate_sums, unsigned num_lu_slots, unsigned num_lut_slots,
+                                unsigned num_luts, size_t lookup_selectors_first_col, const uint64_t *deltas,
+                                const uint64_t *lut_re_poly_evals, uint64_t *values_out, p2hot_cols **chunks_out);
+/* a's columns followed by b's (same degree, same context) as a NEW owned set; a and b stay valid.  The Zs / partial products and the
+ * lookup polynomials go into one commitment (prover.rs:237-241): concat, then p2hot_commit_cols(is_values = 1). */
+int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2hot_cols *b, p2hot_cols **out);
 
 /* ================================================================ multi-GPU: the coset-sharded commit
  * The rate-1/B LDE is B independent coset transforms and coset j is the contiguous row block bitrev(j) of the

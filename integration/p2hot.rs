@@ -57,6 +57,8 @@ use crate::fri::oracle::{PolynomialBatch, SALT_SIZE};
 use crate::fri::proof::{FriInitialTreeProof, FriProof, FriQueryRound, FriQueryStep};
 use crate::fri::structure::FriInstanceInfo;
 use crate::fri::FriParams;
+use crate::gates::lookup::LookupGate;
+use crate::gates::lookup_table::LookupTableGate;
 use crate::hash::hash_types::RichField;
 use crate::hash::hashing::PlonkyPermutation;
 use crate::hash::keccak::KeccakHash;
@@ -65,10 +67,11 @@ use crate::hash::merkle_tree::{MerkleCap, MerkleTree};
 use crate::hash::poseidon::PoseidonHash;
 use crate::iop::challenger::Challenger;
 use crate::iop::witness::MatrixWitness;
+use crate::plonk::circuit_builder::{LookupChallenges, NUM_COINS_LOOKUP};
 use crate::plonk::circuit_data::{CommonCircuitData, ProverOnlyCircuitData};
 use crate::plonk::config::{GenericConfig, GenericHashOut, Hasher};
 use crate::plonk::plonk_common::reduce_with_powers_multi;
-use crate::plonk::vanishing_poly::evaluate_gate_constraints_base_batch;
+use crate::plonk::vanishing_poly::{evaluate_gate_constraints_base_batch, get_lut_poly};
 use crate::plonk::vars::EvaluationVarsBaseBatch;
 use crate::util::strided_view::PackedStridedView;
 use crate::util::{log2_ceil, log2_strict, reverse_bits};
@@ -338,6 +341,18 @@ extern "C" {
         k_is: *const u64, num_routed: c_uint, quotient_degree_factor: c_uint, betas: *const u64, gammas: *const u64, alphas: *const u64,
         num_challenges: c_uint, gate_sums: *const *const u64, values_out: *mut u64, chunks_out: *mut *mut P2hotCols,
     ) -> c_int;
+    pub fn p2hot_lookup_polys(
+        ctx: *mut P2hotCtx, wires: *const P2hotCols, wires_first_col: usize, num_lu_slots: c_uint, num_lut_slots: c_uint, lookup_degree: c_uint,
+        lookup_rows: *const u64, num_luts: c_uint, deltas: *const u64, num_challenges: c_uint, out_host: *mut u64, out_cols: *mut *mut P2hotCols,
+    ) -> c_int;
+    pub fn p2hot_quotient_polys_lookup(
+        ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize,
+        zs_partial_products_lookups: *const P2hotBatch, k_is: *const u64, num_routed: c_uint, quotient_degree_factor: c_uint, betas: *const u64,
+        gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gate_sums: *const *const u64, num_lu_slots: c_uint, num_lut_slots: c_uint,
+        num_luts: c_uint, lookup_selectors_first_col: usize, deltas: *const u64, lut_re_poly_evals: *const u64, values_out: *mut u64,
+        chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
+    pub fn p2hot_cols_concat(ctx: *mut P2hotCtx, a: *const P2hotCols, b: *const P2hotCols, out: *mut *mut P2hotCols) -> c_int;
     // ---- multi-GPU
     pub fn p2hot_comm_unique_id(out: *mut u8) -> c_int;
     pub fn p2hot_comm_create_rccl(ctx: *mut P2hotCtx, rank: c_int, world: c_int, id: *const u8, out: *mut *mut P2hotComm) -> c_int;
@@ -1175,6 +1190,51 @@ pub fn all_wires_permutation_partial_products<F: RichField + Extendable<D>, C: G
     Some((0..nc).map(|c| (0..num_prods).map(|p| col(nc + c * num_prods + p)).chain(core::iter::once(col(c))).collect()).collect())
 }
 
+/// `compute_all_lookup_polys` (plonk/prover.rs:577-605) as ONE `p2hot_lookup_polys` call: RE and the partial SLDC polynomials of
+/// every challenge from the routed wire columns as they lie in the witness (lane = row, one inversion per slot group, the row walk
+/// of prover.rs:488-570 as a suffix scan per LUT, the LUTs in `prover_data.lookup_rows` order).  Returns the reference's result --
+/// per challenge RE, then the SLDCs -- or `None` for the CPU body.  A zero `alpha - combo` panics here as
+/// `batch_multiplicative_inverse` does there.
+pub fn compute_all_lookup_polys<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>(
+    witness: &MatrixWitness<F>,
+    deltas: &[F],
+    prover_data: &ProverOnlyCircuitData<F, C, D>,
+    common_data: &CommonCircuitData<F, D>,
+) -> Option<Vec<PolynomialValues<F>>> {
+    if !applies::<F, C, D>(false) {
+        return None;
+    }
+    let nc = common_data.config.num_challenges;
+    if nc == 0 || nc > 4 || common_data.config.max_quotient_degree_factor < 2 {
+        return None;
+    }
+    let num_lu_slots = LookupGate::num_slots(&common_data.config);
+    let num_lut_slots = LookupTableGate::num_slots(&common_data.config);
+    let lookup_degree = common_data.config.max_quotient_degree_factor - 1; // prover.rs:470
+    let num_polys = num_lu_slots.div_ceil(lookup_degree) + 1; // RE + the partial SLDCs (prover.rs:471-479)
+    let n = 1usize << common_data.degree_bits();
+    let num_cols = (2 * num_lu_slots).max(3 * num_lut_slots);
+    assert!(deltas.len() == nc * NUM_COINS_LOOKUP && witness.wire_values.len() >= num_cols);
+    assert!(witness.wire_values[..num_cols].iter().all(|c| c.len() == n));
+    let wire_ptrs: Vec<*const u64> = witness.wire_values[..num_cols].iter().map(|c| words(c)).collect();
+    let rows: Vec<u64> = prover_data.lookup_rows.iter().flat_map(|w| [w.last_lu_gate as u64, w.last_lut_gate as u64, w.first_lut_gate as u64]).collect();
+    let d: Vec<u64> = deltas.iter().map(|x| x.to_canonical_u64()).collect();
+    let flat: Vec<F> = vec_from_words(nc * num_polys * n, |out| {
+        with_ctx(|ctx| {
+            let mut wires = ColsGuard(core::ptr::null_mut());
+            check(ctx, unsafe { p2hot_cols_upload(ctx, wire_ptrs.as_ptr(), num_cols, log2_strict(n) as c_uint, &mut wires.0) }, "p2hot_cols_upload");
+            let rc = unsafe {
+                p2hot_lookup_polys(
+                    ctx, wires.0, 0, num_lu_slots as c_uint, num_lut_slots as c_uint, lookup_degree as c_uint, rows.as_ptr(),
+                    prover_data.lookup_rows.len() as c_uint, d.as_ptr(), nc as c_uint, out, core::ptr::null_mut(),
+                )
+            };
+            check(ctx, rc, "p2hot_lookup_polys"); // "Tried to invert zero" panics here as on the CPU path
+        })
+    });
+    Some(flat.par_chunks_exact(n).map(|c| PolynomialValues::new(c.to_vec())).collect())
+}
+
 // ------------------------------------------------------------------------------------------------
 // OpeningSet::new (plonk/proof.rs:314-351): `eval_commitment` on the GPU
 // ------------------------------------------------------------------------------------------------
@@ -1208,8 +1268,9 @@ pub fn eval_commitment<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>,
 /// (prover.rs:684-779, BATCH_SIZE = 32) and reduced on their own; everything in front of them -- 80 routed wires x 2 challenges at
 /// 2^23 points for a 2^20-gate circuit -- and the division by Z_H, the coset_ifft and the trim run in ONE `p2hot_quotient_polys`
 /// call on the LDE matrices the three commitments already hold on the device.  Returns the reference's result (one polynomial of
-/// `quotient_degree_factor * n` coefficients per challenge); `None` sends the caller down the CPU body (lookups, a commitment
-/// without a device handle, more than 4 challenges).
+/// `quotient_degree_factor * n` coefficients per challenge); `None` sends the caller down the CPU body (a commitment without a
+/// device handle, more than 4 challenges).  A circuit with lookup tables takes `p2hot_quotient_polys_lookup`: the same call with the
+/// terms of `check_lookup_constraints_batch` between the partial-product terms and the gate terms.
 pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize>(
     common_data: &CommonCircuitData<F, D>,
     prover_data: &ProverOnlyCircuitData<F, C, D>,
@@ -1218,11 +1279,13 @@ pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, 
     zs_partial_products_commitment: &PolynomialBatch<F, C, D>,
     betas: &[F],
     gammas: &[F],
+    deltas: &[F],
     alphas: &[F],
 ) -> Option<Vec<PolynomialCoeffs<F>>> {
-    if !applies::<F, C, D>(false) || common_data.num_lookup_polys != 0 {
+    if !applies::<F, C, D>(false) {
         return None;
     }
+    let has_lookup = common_data.num_lookup_polys != 0;
     let cs = &prover_data.constants_sigmas_commitment;
     let h_wires = wires_commitment.merkle_tree.device.as_ref()?.raw();
     let h_cs = cs.merkle_tree.device.as_ref()?.raw();
@@ -1233,6 +1296,15 @@ pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, 
     let rate_bits = common_data.config.fri_config.rate_bits;
     if nc > 4 || quotient_degree_bits > rate_bits {
         return None; // (the CPU body asserts on the second, prover.rs:632-636)
+    }
+    if has_lookup {
+        // the library derives the number of partial SLDC polynomials from quotient_degree_factor - 1 (vanishing_poly.rs:526); the
+        // prover made them with max_quotient_degree_factor - 1 (prover.rs:470): when the two disagree, or the lookup selectors are
+        // not where num_selectors() puts them, the CPU body runs
+        let s = LookupGate::num_slots(&common_data.config).div_ceil(qdf - 1);
+        if common_data.num_lookup_polys != s + 1 || common_data.num_lookup_selectors != 4 + common_data.luts.len() || deltas.len() != nc * NUM_COINS_LOOKUP {
+            return None;
+        }
     }
     assert!(betas.len() == nc && gammas.len() == nc && alphas.len() == nc);
     let n = 1usize << common_data.degree_bits();
@@ -1277,14 +1349,47 @@ pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, 
     let k_is: Vec<u64> = common_data.k_is[..num_routed].iter().map(|k| k.to_canonical_u64()).collect();
     let to_u64 = |v: &[F]| -> Vec<u64> { v.iter().map(|x| x.to_canonical_u64()).collect() };
     let (b, g, a) = (to_u64(betas), to_u64(gammas), to_u64(alphas));
+    // the lookup argument (vanishing_poly.rs:515-664): its terms run on the GPU between the permutation terms and the gate terms;
+    // lut_re_poly_evals[c][r] = get_lut_poly(..).eval(delta_c) as the CPU body precomputes them (prover.rs:652-680)
+    let num_lu_slots = LookupGate::num_slots(&common_data.config);
+    let num_lut_slots = LookupTableGate::num_slots(&common_data.config);
+    let num_luts = common_data.luts.len();
+    let d = to_u64(deltas);
+    let lut_re_poly_evals: Vec<u64> = if has_lookup {
+        (0..nc)
+            .flat_map(|i| {
+                let cur_deltas = &deltas[NUM_COINS_LOOKUP * i..NUM_COINS_LOOKUP * (i + 1)];
+                let cur_challenge_delta = cur_deltas[LookupChallenges::ChallengeDelta as usize];
+                (0..num_luts)
+                    .map(|r| {
+                        let lut_row_number = common_data.luts[r].len().div_ceil(num_lut_slots);
+                        get_lut_poly(common_data, r, cur_deltas, num_lut_slots * lut_row_number).eval(cur_challenge_delta).to_canonical_u64()
+                    })
+                    .collect::<Vec<u64>>()
+            })
+            .collect()
+    } else {
+        Vec::new()
+    };
     let coeffs: Vec<F> = vec_from_words(nc * qdf * n, |out| {
         with_ctx(|ctx| {
             let mut chunks = ColsGuard(core::ptr::null_mut()); // freed on every path, the panicking ones included
-            let rc = unsafe {
-                p2hot_quotient_polys(
-                    ctx, h_wires, h_cs, common_data.sigmas_range().start, h_zs, k_is.as_ptr(), num_routed as c_uint, qdf as c_uint,
-                    b.as_ptr(), g.as_ptr(), a.as_ptr(), nc as c_uint, gate_ptrs.as_ptr(), core::ptr::null_mut(), &mut chunks.0,
-                )
+            let rc = if has_lookup {
+                unsafe {
+                    p2hot_quotient_polys_lookup(
+                        ctx, h_wires, h_cs, common_data.sigmas_range().start, h_zs, k_is.as_ptr(), num_routed as c_uint, qdf as c_uint,
+                        b.as_ptr(), g.as_ptr(), a.as_ptr(), nc as c_uint, gate_ptrs.as_ptr(), num_lu_slots as c_uint, num_lut_slots as c_uint,
+                        num_luts as c_uint, common_data.selectors_info.num_selectors(), d.as_ptr(), lut_re_poly_evals.as_ptr(),
+                        core::ptr::null_mut(), &mut chunks.0,
+                    )
+                }
+            } else {
+                unsafe {
+                    p2hot_quotient_polys(
+                        ctx, h_wires, h_cs, common_data.sigmas_range().start, h_zs, k_is.as_ptr(), num_routed as c_uint, qdf as c_uint,
+                        b.as_ptr(), g.as_ptr(), a.as_ptr(), nc as c_uint, gate_ptrs.as_ptr(), core::ptr::null_mut(), &mut chunks.0,
+                    )
+                }
             };
             check(ctx, rc, "p2hot_quotient_polys"); // "Quotient has failed ..." panics here as trim_to_len does on the CPU path
             check(ctx, unsafe { p2hot_cols_download(chunks.0, 0, nc * qdf, out) }, "p2hot_cols_download");

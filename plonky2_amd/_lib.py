@@ -138,6 +138,10 @@ SIGNATURES = {
     "p2hot_partial_products": (i, [vp, vp, sz, vp, sz, vp, u, u, vp, vp, u, vp, C.POINTER(vp)]),
     "p2hot_quotient_chunks": (i, [vp, C.POINTER(vp), u, u, u, C.POINTER(vp)]),
     "p2hot_quotient_polys": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), vp, C.POINTER(vp)]),
+    "p2hot_lookup_polys": (i, [vp, vp, sz, u, u, u, vp, u, vp, u, vp, C.POINTER(vp)]),
+    "p2hot_quotient_polys_lookup": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), u, u, u, sz, vp, vp, vp,
+                                        C.POINTER(vp)]),
+    "p2hot_cols_concat": (i, [vp, vp, vp, C.POINTER(vp)]),
     "p2hot_comm_unique_id": (i, [vp]),
     "p2hot_comm_create_rccl": (i, [vp, i, i, vp, C.POINTER(vp)]),
     "p2hot_comm_create_callback": (i, [vp, i, i, ALLGATHER_FN, vp, C.POINTER(vp)]),

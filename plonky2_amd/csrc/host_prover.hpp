@@ -1378,10 +1378,18 @@ extern "C" int p2hot_quotient_chunks(p2hot_ctx *ctx, const uint64_t *const *quot
 // compute_quotient_polys (plonky2/src/plonk/prover.rs:609-815) without its gate evaluation: the permutation argument's vanishing
 // terms on the quotient coset (plonk/vanishing_poly.rs:167-330; kernel: plonk::quotient_perm_kernel) from the three commitments'
 // device-resident LDE matrices, plus the caller's reduced gate terms, over Z_H; then the same tail as p2hot_quotient_chunks.
-extern "C" int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
-                                    const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
-                                    unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
-                                    unsigned num_challenges, const uint64_t *const *gate_sums, uint64_t *values_out, p2hot_cols **chunks_out) {
+// `lk` (p2hot_quotient_polys_lookup): the lookup argument's terms (lookup::lookup_terms_kernel) go between the permutation terms and
+// the gate terms; null = p2hot_quotient_polys
+struct LookupQuot {
+    unsigned num_lu_slots, num_lut_slots, num_luts;
+    size_t selectors_first_col;
+    const uint64_t *deltas, *lut_re_poly_evals;
+};
+static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                               const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
+                               unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                               unsigned num_challenges, const uint64_t *const *gate_sums, uint64_t *values_out, p2hot_cols **chunks_out,
+                               const LookupQuot *lk) {
     P2_ENTER(ctx);
     if (chunks_out) *chunks_out = nullptr;
     if (!wires || !constants_sigmas || !zs_partial_products || !k_is || !betas || !gammas || !alphas) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys: null argument");
@@ -1391,6 +1399,7 @@ extern "C" int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, co
         if (b->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys: a commitment belongs to another context");
         if (b->log_n != wires->log_n || b->rate_bits != wires->rate_bits) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys: the commitments differ in degree or rate");
     }
+    if (lk && (num_challenges == 0 || num_challenges > 4)) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: %u challenges (1..4)", num_challenges);
     if (num_challenges == 0 || num_challenges > 4) P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "quotient_polys: %u challenges (1..4 supported; plonky2's configs use 2)", num_challenges);
     if (quotient_degree_factor < 2 || num_routed == 0) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys: bad quotient degree factor or no routed wires");
     unsigned qbits = 0;
@@ -1404,13 +1413,31 @@ extern "C" int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, co
     const size_t n = (size_t)1 << degree_bits, m = n << qbits, rate = (size_t)1 << qbits;
     for (unsigned c = 0; c < num_challenges && gate_sums; ++c)
         if (!gate_sums[c]) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys: gate_sums[%u] is null", c);
+    // the lookup argument (vanishing_poly.rs:515-664): S partial SLDC polynomials + RE per challenge behind the partial products
+    unsigned lk_S = 0, lk_Kc = 0;
+    if (lk) {
+        for (const p2hot_batch *b : bs)
+            if (b->hash_n) P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "quotient_polys_lookup: KeccakHash commitments are not supported");
+        if (!lk->deltas || (lk->num_luts && !lk->lut_re_poly_evals)) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: null argument");
+        const unsigned lookup_degree = quotient_degree_factor - 1;  // vanishing_poly.rs:526
+        if (lk->num_lu_slots == 0 || lk->num_lut_slots == 0) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: no lookup slots");
+        if ((size_t)2 * lk->num_lu_slots > wires->W || (size_t)3 * lk->num_lut_slots > wires->W)
+            P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: %u LookupGate / %u LookupTableGate slots do not fit %zu wires", lk->num_lu_slots, lk->num_lut_slots, wires->W);
+        lk_S = (lk->num_lu_slots + lookup_degree - 1) / lookup_degree;
+        lk_Kc = 4 + lk->num_luts + 2 * lk_S;
+        if (zs_partial_products->W != (size_t)num_challenges * (1 + num_prods) + (size_t)num_challenges * (lk_S + 1))
+            P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: the Zs batch has %zu polynomials, not nc (1 + %u) + nc (%u + 1)", zs_partial_products->W, num_prods, lk_S);
+        if (lk->selectors_first_col > constants_sigmas->W || (size_t)4 + lk->num_luts > constants_sigmas->W - lk->selectors_first_col)
+            P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: the lookup selectors do not fit the constants_sigmas commitment");
+    }
+    const size_t n_apow = lk ? (size_t)num_challenges * ((size_t)num_challenges * lk_Kc + 1) : 0, n_evals = lk ? (size_t)num_challenges * lk->num_luts : 0;
     PoolBuf d_work(ctx), d_small(ctx), d_gate(ctx);
     P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8 + 8, &d_work.p));
     const size_t nbk = (size_t)num_challenges * num_routed;
-    P2_TRY(pool_alloc(ctx, (nbk + 2 * rate) * 8, &d_small.p));
-    if (gate_sums) P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8, &d_gate.p));
+    P2_TRY(pool_alloc(ctx, (nbk + 2 * rate + n_apow + n_evals) * 8, &d_small.p));
+    if (gate_sums || lk) P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8, &d_gate.p));
     // ZeroPolyOnCoset::new(degree_bits, qbits) (field/src/zero_poly_coset.rs:21-34) and beta_c * k_j, on the host
-    std::vector<u64> small(nbk + 2 * rate);
+    std::vector<u64> small(nbk + 2 * rate + n_apow + n_evals);
     for (unsigned c = 0; c < num_challenges; ++c)
         for (unsigned j = 0; j < num_routed; ++j) small[(size_t)c * num_routed + j] = gl::canon(gl::mul(betas[c], k_is[j]));
     const size_t num_routed_ = nbk;  // (offset of the Z_H table behind the beta * k table)
@@ -1439,7 +1466,7 @@ extern "C" int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, co
     q.sigmas = constants_sigmas->d_lde + sigmas_first_col * constants_sigmas->col_stride_lde(), q.sigmas_stride = constants_sigmas->col_stride_lde();
     q.zs = zs_partial_products->d_lde, q.zs_stride = zs_partial_products->col_stride_lde();
     q.bk = d_small.u(), q.zh = d_small.u() + nbk, q.inv_nx1 = inv_it->second;
-    q.gate_sums = gate_sums ? d_gate.u() : nullptr;
+    q.gate_sums = gate_sums || lk ? d_gate.u() : nullptr;
     q.out = d_work.u();
     q.num_routed = num_routed, q.degree = quotient_degree_factor, q.num_chunks = num_chunks, q.log_nq = log_nq, q.qbits = qbits;
     const u64 K = (u64)num_challenges + (u64)num_challenges * num_chunks;
@@ -1449,10 +1476,41 @@ extern "C" int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, co
         for (unsigned c = 0; c < num_challenges; ++c) q.base[a][c] = gl::pow(alphas[a], (u64)num_challenges + (u64)c * num_chunks);
     }
     q.roots = ctx->fwd;
+    lookup::TermArgs lt{};
+    if (lk) {
+        const unsigned Klu = num_challenges * lk_Kc;
+        u64 *apow = small.data() + nbk + 2 * rate, *evals = apow + n_apow;
+        for (unsigned a = 0; a < num_challenges; ++a) {
+            u64 pw = 1;
+            for (unsigned t = 0; t <= Klu; ++t, pw = gl::mul(pw, alphas[a])) apow[(size_t)a * (Klu + 1) + t] = gl::canon(pw);
+        }
+        for (size_t k = 0; k < n_evals; ++k) evals[k] = gl::canon(lk->lut_re_poly_evals[k]);
+        lt.wires = wires->d_lde, lt.wires_stride = wires->col_stride_lde();
+        lt.sel = constants_sigmas->d_lde + lk->selectors_first_col * constants_sigmas->col_stride_lde(), lt.sel_stride = constants_sigmas->col_stride_lde();
+        lt.lz_stride = zs_partial_products->col_stride_lde();
+        lt.lz = zs_partial_products->d_lde + (size_t)num_challenges * (1 + num_prods) * lt.lz_stride;
+        lt.apow = d_small.u() + nbk + 2 * rate, lt.lut_evals = lt.apow + n_apow;
+        lt.gate_sums = gate_sums ? d_gate.u() : nullptr, lt.out = d_gate.u();
+        lt.num_lu_slots = lk->num_lu_slots, lt.num_lut_slots = lk->num_lut_slots, lt.lu_degree = quotient_degree_factor - 1;
+        lt.S = lk_S, lt.lut_degree = (lk->num_lut_slots + lk_S - 1) / lk_S, lt.num_luts = lk->num_luts, lt.log_nq = log_nq, lt.qbits = qbits;
+        for (unsigned c = 0; c < num_challenges; ++c)
+            for (unsigned k = 0; k < 4; ++k) lt.deltas[c][k] = gl::canon(lk->deltas[(size_t)c * 4 + k]);
+    }
     auto body = [&]() -> int {
         P2_HIP(ctx, hipMemcpyAsync(d_small.p, small.data(), small.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         for (unsigned c = 0; c < num_challenges && gate_sums; ++c)
             P2_HIP(ctx, hipMemcpyAsync(d_gate.u() + (size_t)c * m, gate_sums[c], m * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (lk) {
+            ProfScope prof(ctx, "quotient_lookup");
+            const dim3 grid(cdiv(m, 256)), block(256);
+            switch (num_challenges) {
+                case 1: P2HOT_LAUNCH((lookup::lookup_terms_kernel<1>), grid, block, 0, ctx->stream, lt); break;
+                case 2: P2HOT_LAUNCH((lookup::lookup_terms_kernel<2>), grid, block, 0, ctx->stream, lt); break;
+                case 3: P2HOT_LAUNCH((lookup::lookup_terms_kernel<3>), grid, block, 0, ctx->stream, lt); break;
+                default: P2HOT_LAUNCH((lookup::lookup_terms_kernel<4>), grid, block, 0, ctx->stream, lt); break;
+            }
+            P2_LAUNCH_CHECK(ctx);
+        }
         ProfScope prof(ctx, "quotient_perm");
         const dim3 grid(cdiv(m, 256)), block(256);
         if (num_challenges == 2 && quotient_degree_factor == 8) {  // every plonky2 config (circuit_data.rs:101-119): the pipelined instantiation
@@ -1472,4 +1530,120 @@ extern "C" int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, co
     int rc = body();
     if (rc != P2HOT_OK || !chunks_out) return sync_checked(ctx, rc, "quotient_polys");
     return quotient_chunks_core(ctx, d_work, num_challenges, degree_bits, qbits, quotient_degree_factor, "quotient_polys", chunks_out);
+}
+
+extern "C" int p2hot_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                    const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
+                                    unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                    unsigned num_challenges, const uint64_t *const *gate_sums, uint64_t *values_out, p2hot_cols **chunks_out) {
+    return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products, k_is, num_routed, quotient_degree_factor, betas,
+                               gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, nullptr);
+}
+
+// compute_quotient_polys (plonk/prover.rs:609-815) for a circuit with lookup tables: p2hot_quotient_polys plus
+// check_lookup_constraints_batch's terms (plonk/vanishing_poly.rs:515-664) in their place of the term list (:317-322)
+extern "C" int p2hot_quotient_polys_lookup(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                           const p2hot_batch *zs_partial_products_lookups, const uint64_t *k_is, unsigned num_routed,
+                                           unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                           unsigned num_challenges, const uint64_t *const *gate_sums, unsigned num_lu_slots, unsigned num_lut_slots,
+                                           unsigned num_luts, size_t lookup_selectors_first_col, const uint64_t *deltas,
+                                           const uint64_t *lut_re_poly_evals, uint64_t *values_out, p2hot_cols **chunks_out) {
+    const LookupQuot lk{num_lu_slots, num_lut_slots, num_luts, lookup_selectors_first_col, deltas, lut_re_poly_evals};
+    return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products_lookups, k_is, num_routed, quotient_degree_factor,
+                               betas, gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, &lk);
+}
+
+// ------------------------------------------------------------------ lookup polynomials (plonk/prover.rs:451-605)
+extern "C" int p2hot_lookup_polys(p2hot_ctx *ctx, const p2hot_cols *wires, size_t wires_first_col, unsigned num_lu_slots, unsigned num_lut_slots,
+                                  unsigned lookup_degree, const uint64_t *lookup_rows, unsigned num_luts, const uint64_t *deltas,
+                                  unsigned num_challenges, uint64_t *out_host, p2hot_cols **out_cols) {
+    P2_ENTER(ctx);
+    if (out_cols) *out_cols = nullptr;
+    if (!wires || wires->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: null or foreign column set");
+    if (!deltas || (num_luts && !lookup_rows)) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: null argument");
+    if (num_challenges == 0 || num_challenges > 4) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: %u challenges (1..4)", num_challenges);
+    if (lookup_degree == 0) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: lookup_degree is 0");
+    if (num_lu_slots == 0 || num_lut_slots == 0) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: no lookup slots");
+    if (wires_first_col > wires->W || (size_t)2 * num_lu_slots > wires->W - wires_first_col || (size_t)3 * num_lut_slots > wires->W - wires_first_col)
+        P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: %u LookupGate / %u LookupTableGate slots do not fit the wires given", num_lu_slots, num_lut_slots);
+    const unsigned log_n = wires->log_n;
+    const size_t n = (size_t)1 << log_n;
+    size_t max_len = 1;
+    for (unsigned r = 0; r < num_luts; ++r) {
+        const uint64_t last_lu = lookup_rows[3 * r], last_lut = lookup_rows[3 * r + 1], first_lut = lookup_rows[3 * r + 2];
+        if (!(last_lu <= last_lut && last_lut <= first_lut)) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: LUT %u: rows not ordered last_lu <= last_lut <= first_lut", r);
+        // prover.rs:517: values[row + 1] at row = first_lut_row
+        if (first_lut >= n || first_lut + 1 >= n) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: LUT %u: first_lut_gate + 1 = %llu is not a row of the trace", r, (unsigned long long)first_lut + 1);
+        max_len = std::max(max_len, (size_t)(first_lut - last_lu + 1));
+    }
+    const unsigned S = (num_lu_slots + lookup_degree - 1) / lookup_degree;
+    const size_t rows = (size_t)num_challenges * (S + 1), max_chunks = (max_len + lookup::SCAN_CHUNK - 1) / lookup::SCAN_CHUNK;
+    PoolBuf d_out(ctx), d_sc(ctx);
+    P2_TRY(pool_alloc(ctx, rows * n * 8, &d_out.p));
+    P2_TRY(pool_alloc(ctx, 5 * (size_t)num_challenges * max_chunks * 8 + 8, &d_sc.p));
+    lookup::PolyArgs a{};
+    a.wires = wires->d + wires_first_col * n, a.wires_stride = n, a.out = d_out.u(), a.out_stride = n;
+    a.num_lu_slots = num_lu_slots, a.num_lut_slots = num_lut_slots, a.lu_degree = lookup_degree, a.S = S;
+    a.lut_degree = (num_lut_slots + S - 1) / S;  // prover.rs:473
+    for (unsigned c = 0; c < num_challenges; ++c) {
+        for (unsigned k = 0; k < 4; ++k) a.deltas[c][k] = gl::canon(deltas[(size_t)c * 4 + k]);
+        a.delta_pow[c] = gl::pow(a.deltas[c][3], num_lut_slots);
+    }
+    unsigned *flag = (unsigned *)(d_sc.u() + 5 * (size_t)num_challenges * max_chunks);
+    a.zero_flag = flag;
+    unsigned zero = 0;
+    auto body = [&]() -> int {
+        ProfScope prof(ctx, "lookup_polys");
+        P2_HIP(ctx, hipMemsetAsync(d_out.p, 0, rows * n * 8, ctx->stream));
+        P2_HIP(ctx, hipMemsetAsync(flag, 0, 8, ctx->stream));
+        // the regions one after the other, in the caller's order: each reads what the earlier ones left at its first_lut + 1
+        for (unsigned r = 0; r < num_luts; ++r) {
+            a.last_lu = lookup_rows[3 * r], a.last_lut = lookup_rows[3 * r + 1], a.first_lut = lookup_rows[3 * r + 2];
+            const size_t len = a.first_lut - a.last_lu + 1;
+            a.n_chunks = (len + lookup::SCAN_CHUNK - 1) / lookup::SCAN_CHUNK;
+            const size_t stride = (size_t)num_challenges * a.n_chunks;
+            a.csum = d_sc.u(), a.cmul = a.csum + stride, a.cadd = a.cmul + stride, a.carry_s = a.cadd + stride, a.carry_re = a.carry_s + stride;
+            P2HOT_LAUNCH(lookup::lookup_rows_kernel, dim3(cdiv(len, 256), num_challenges), dim3(256), 0, ctx->stream, a);
+            P2_LAUNCH_CHECK(ctx);
+            P2HOT_LAUNCH(lookup::lookup_chunk_totals_kernel, dim3(cdiv(a.n_chunks, 64), num_challenges), dim3(64), 0, ctx->stream, a);
+            P2_LAUNCH_CHECK(ctx);
+            P2HOT_LAUNCH(lookup::lookup_carries_kernel, dim3(num_challenges), dim3(1024), 0, ctx->stream, a, (a.n_chunks + 1023) / 1024);
+            P2_LAUNCH_CHECK(ctx);
+            P2HOT_LAUNCH(lookup::lookup_emit_kernel, dim3(cdiv(a.n_chunks, 64), num_challenges), dim3(64), 0, ctx->stream, a);
+            P2_LAUNCH_CHECK(ctx);
+        }
+        P2_HIP(ctx, hipMemcpyAsync(&zero, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_host) P2_HIP(ctx, hipMemcpyAsync(out_host, d_out.p, rows * n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return P2HOT_OK;
+    };
+    int rc = sync_checked(ctx, body(), "lookup_polys");
+    if (rc != P2HOT_OK) return rc;
+    if (zero) P2_FAIL(ctx, P2HOT_EINVAL, "lookup_polys: Tried to invert zero (alpha equals a looked or looking combination; the reference panics in batch_multiplicative_inverse)");
+    if (out_cols) {
+        *out_cols = new p2hot_cols{ctx, d_out.u(), rows, log_n, true};
+        d_out.p = nullptr;
+    }
+    return rc;
+}
+
+// a's columns then b's as one new set (prover.rs:237-241: Zs / partial products ++ lookup polys go into ONE commitment); the
+// inputs are left as they are
+extern "C" int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2hot_cols *b, p2hot_cols **out) {
+    P2_ENTER(ctx);
+    if (!out) P2_FAIL(ctx, P2HOT_EINVAL, "cols_concat: null output");
+    *out = nullptr;
+    if (!a || !b || a->ctx != ctx || b->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "cols_concat: null or foreign column set");
+    if (a->log_n != b->log_n) P2_FAIL(ctx, P2HOT_EINVAL, "cols_concat: the sets differ in degree (2^%u and 2^%u rows)", a->log_n, b->log_n);
+    const size_t n = (size_t)1 << a->log_n;
+    PoolBuf d(ctx);
+    P2_TRY(pool_alloc(ctx, (a->W + b->W) * n * 8, &d.p));
+    auto body = [&]() -> int {
+        if (a->W) P2_HIP(ctx, hipMemcpyAsync(d.u(), a->d, a->W * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        if (b->W) P2_HIP(ctx, hipMemcpyAsync(d.u() + a->W * n, b->d, b->W * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        return P2HOT_OK;
+    };
+    P2_TRY(sync_checked(ctx, body(), "cols_concat"));
+    *out = new p2hot_cols{ctx, d.u(), a->W + b->W, a->log_n, true};
+    d.p = nullptr;
+    return P2HOT_OK;
 }

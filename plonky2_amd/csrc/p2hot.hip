@@ -16,6 +16,7 @@
 
 #include "fri.hpp"
 #include "plonk.hpp"
+#include "lookup.hpp"
 #include "merkle.hpp"
 #include "keccak.hpp"
 #include "ntt.hpp"

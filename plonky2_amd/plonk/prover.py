@@ -136,3 +136,91 @@ def compute_quotient_polys(wires_commitment, constants_sigmas_commitment, sigmas
     eng.check(rc)
     cols = DeviceColumns(eng, h)
     return (cols, vals) if want_values else cols
+
+
+# ------------------------------------------------------------------ the lookup argument
+def num_sldc_polys(num_lu_slots, lookup_degree):
+    """prover.rs:471 / vanishing_poly.rs:527: the partial SLDC polynomials of one challenge"""
+    return -(-num_lu_slots // lookup_degree)
+
+
+def concat_columns(a, b, engine=None):
+    """p2hot_cols_concat: a's columns then b's as new DeviceColumns (the Zs / partial products ++ the lookup polynomials of
+    prover.rs:237-241, for one PolynomialBatch.from_values); a and b stay valid"""
+    from ..fri.oracle import DeviceColumns
+    eng = engine or a.engine
+    h = C.c_void_p()
+    eng.check(eng.lib.p2hot_cols_concat(eng.ctx, a._h, b._h, C.byref(h)))
+    return DeviceColumns(eng, h)
+
+
+def all_lookup_polys(wires, lookup_rows, deltas, num_lu_slots, num_lut_slots, lookup_degree, want_host=False, engine=None):
+    """compute_all_lookup_polys (prover.rs:451-605) -- one p2hot_lookup_polys call.
+
+    wires: [>= max(2 num_lu_slots, 3 num_lut_slots)][n] wire columns (host ndarray or DeviceColumns); lookup_rows: per LUT
+    (last_lu_gate, last_lut_gate, first_lut_gate) in prover_data.lookup_rows order; deltas: [num_challenges][4] = A, B, Alpha,
+    Delta; lookup_degree = max_quotient_degree_factor - 1.  Returns DeviceColumns [num_challenges * (S + 1)][n]: RE and the S
+    partial SLDC polynomials of challenge 0, 1, ... (and the same as a host array when want_host).  A zero alpha - combination
+    raises ValueError("Tried to invert zero"), where the reference panics."""
+    from ..fri.oracle import DeviceColumns
+    eng = engine or default_engine()
+    dw = wires if isinstance(wires, DeviceColumns) else DeviceColumns.upload(eng.host(wires), eng)
+    rows = np.ascontiguousarray(np.asarray(lookup_rows, dtype=np.uint64).reshape(-1, 3))
+    d = np.ascontiguousarray(np.asarray(deltas, dtype=np.uint64))
+    if d.ndim != 2 or d.shape[1] != 4:
+        raise ValueError("deltas must be [num_challenges][4]")
+    nc = d.shape[0]
+    out = None
+    if want_host and lookup_degree > 0 and 1 <= nc <= 4:
+        out = np.zeros((nc * (num_sldc_polys(num_lu_slots, lookup_degree) + 1), 1 << dw.degree_log), dtype=np.uint64)
+    h = C.c_void_p()
+    rc = eng.lib.p2hot_lookup_polys(eng.ctx, dw._h, 0, num_lu_slots, num_lut_slots, lookup_degree, rows.ctypes.data_as(C.c_void_p),
+                                    len(rows), d.ctypes.data_as(C.c_void_p), nc, out.ctypes.data_as(C.c_void_p) if out is not None else None,
+                                    C.byref(h))
+    if rc == 1 and b"Tried to invert zero" in eng.lib.p2hot_last_error(eng._ctx):
+        raise ValueError(eng.lib.p2hot_last_error(eng._ctx).decode())  # the reference panics (field/src/types.rs:133)
+    eng.check(rc)
+    cols = DeviceColumns(eng, h)
+    return (cols, out) if want_host else cols
+
+
+def compute_quotient_polys_lookup(wires_commitment, constants_sigmas_commitment, sigmas_first_col, zs_partial_products_lookups_commitment,
+                                  k_is, quotient_degree_factor, betas, gammas, alphas, num_lu_slots, num_lut_slots,
+                                  lookup_selectors_first_col, deltas, lut_re_poly_evals, gate_sums=None, want_values=False, engine=None):
+    """compute_quotient_polys (prover.rs:609-815) of a circuit with lookup tables -- one p2hot_quotient_polys_lookup call:
+    compute_quotient_polys above plus the terms of check_lookup_constraints_batch (vanishing_poly.rs:515-664) between the
+    partial-product terms and the gate terms.  The third commitment holds the Zs, the partial products and the lookup polynomials
+    (all_lookup_polys' order); the 4 + num_luts lookup selectors are columns lookup_selectors_first_col .. of constants_sigmas;
+    deltas [num_challenges][4]; lut_re_poly_evals [num_challenges][num_luts] = get_lut_poly(..).eval(delta).  Returns as
+    compute_quotient_polys does."""
+    from ..fri.oracle import DeviceColumns
+    eng = engine or wires_commitment.engine
+    k = np.ascontiguousarray(np.asarray(k_is, dtype=np.uint64))
+    b, g, a = (np.ascontiguousarray(np.asarray(v, dtype=np.uint64)) for v in (betas, gammas, alphas))
+    if not (b.shape == g.shape == a.shape and b.ndim == 1):
+        raise ValueError("betas, gammas and alphas must be equally long vectors")
+    nc = len(b)
+    d = np.ascontiguousarray(np.asarray(deltas, dtype=np.uint64))
+    ev = np.ascontiguousarray(np.asarray(lut_re_poly_evals, dtype=np.uint64).reshape(nc, -1))
+    if d.shape != (nc, 4):
+        raise ValueError("deltas must be [num_challenges][4]")
+    qb = max(0, (quotient_degree_factor - 1).bit_length())
+    m = (1 << wires_commitment.degree_log) << qb
+    gs = None
+    if gate_sums is not None:
+        gs = np.ascontiguousarray(np.asarray(gate_sums, dtype=np.uint64))
+        if gs.shape != (nc, m):
+            raise ValueError("gate_sums must be [num_challenges][n << ceil(log2(quotient_degree_factor))]")
+    gptrs = (C.c_void_p * max(nc, 1))(*[gs[c].ctypes.data for c in range(nc)]) if gs is not None else None
+    vals = np.zeros((nc, m), dtype=np.uint64) if want_values else None
+    h = C.c_void_p()
+    rc = eng.lib.p2hot_quotient_polys_lookup(
+        eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, zs_partial_products_lookups_commitment._h,
+        k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+        a.ctypes.data_as(C.c_void_p), nc, gptrs, num_lu_slots, num_lut_slots, ev.shape[1], lookup_selectors_first_col,
+        d.ctypes.data_as(C.c_void_p), ev.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p) if want_values else None, C.byref(h))
+    if rc == 1 and b"Quotient has failed" in eng.lib.p2hot_last_error(eng._ctx):
+        raise ValueError(eng.lib.p2hot_last_error(eng._ctx).decode())  # the reference panics (polynomial/mod.rs:164-178)
+    eng.check(rc)
+    cols = DeviceColumns(eng, h)
+    return (cols, vals) if want_values else cols

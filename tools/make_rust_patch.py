@@ -6,8 +6,9 @@ The patch is the Rust side of the drop-in boundary: Cargo feature `p
   fri/oracle.rs        from_values / from_coeffs / get_lde_values / prove_openings
   fri/prover.rs        fri_committed_trees
   plonk/proof.rs       OpeningSet::new: eval_commitment through p2hot_eval_openings
-  plonk/prover.rs      all_wires_permutation_partial_products through p2hot_partial_products;
-                       compute_quotient_polys: the gate terms on the CPU, the permutation terms + coset_ifft on the GPU
+  plonk/prover.rs      all_wires_permutation_partial_products through p2hot_partial_products; compute_all_lookup_polys through
+                       p2hot_lookup_polys; compute_quotient_polys: the gate terms on the CPU, the permutation and lookup terms +
+                       coset_ifft on the GPU
   hash/merkle_tree.rs  `device` handle on MerkleTree, get / num_leaves / prove (the leaf matrix may be ONE flat buffer behind it)
   iop/challenger.rs    accessor for the transcript state
   util/serialization   the one other MerkleTree struct literal; write_merkle_tree reads rows through get / num_leaves
@@ -205,14 +206,31 @@ fn main() {
         zs_partial_products_and_lookup_commitment,
         betas,
         gammas,
+        deltas,
         alphas,
     ) {
-        // the permutation terms of the vanishing polynomial, / Z_H, coset_ifft ran on the GPU; the gate terms on the CPU
+        // the permutation and lookup terms of the vanishing polynomial, / Z_H, coset_ifft ran on the GPU; the gate terms on the CPU
         return quotient_polys;
     }
     let num_challenges = common_data.config.num_challenges;
 
     let has_lookup = common_data.num_lookup_polys != 0;
+''')])
+    # ---- the lookup argument's polynomials
+    edit(os.path.join(b, "plonky2/src/plonk/prover.rs"), [
+        ('''    lookup: bool,
+) -> Vec<PolynomialValues<F>> {
+    if lookup {
+''', '''    lookup: bool,
+) -> Vec<PolynomialValues<F>> {
+    #[cfg(feature = "p2hot")]
+    if lookup {
+        if let Some(polys) = crate::p2hot::compute_all_lookup_polys::<F, C, D>(witness, deltas, prover_data, common_data) {
+            // RE and the partial SLDC polynomials of every challenge: the row walk per LUT as a scan on the GPU
+            return polys;
+        }
+    }
+    if lookup {
 ''')])
     # ---- FRI commit phase
     edit(os.path.join(b, "plonky2/src/fri/prover.rs"), [
