@@ -279,7 +279,8 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * A context runs ONE host-pointer call at a time; a second thread entering gets P2HOT_EBUSY (plonky2 calls these
  * from the main thread, outside its rayon closures).  Serialised by the library (busy guard): p2hot_commit*, p2hot_cols_upload,
  * p2hot_batch_coeffs / _rows / _paths / _digests / _subgroup_values, p2hot_eval_openings, p2hot_prove_openings, p2hot_partial_products,
- * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_quotient_polys_lookup, p2hot_lookup_polys, p2hot_cols_concat, p2hot_ctx_trim.  p2hot_batch_free / p2hot_cols_free may be called from any thread at any time (a
+ * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_quotient_polys_lookup, p2hot_lookup_polys, p2hot_cols_concat, p2hot_gate_sums,
+ * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_ctx_trim.  p2hot_batch_free / p2hot_cols_free may be called from any thread at any time (a
  * Drop, a finaliser): the block cache has its own lock.  Everything else -- the *_dev building blocks, p2hot_fri_commit,
  * p2hot_fri_pow, p2hot_challenger_* -- enqueues on the context's stream without a guard: the CALLER serialises those with
  * each other and with the host-pointer calls of the same context (the Rust shim holds the context behind a Mutex). */
@@ -566,6 +567,67 @@ int p2hot_quotient_polys_lookup(p2hot_ctx *ctx, const p2hot_batch *wires, const 
 /* a's columns followed by b's (same degree, same context) as a NEW owned set; a and b stay valid.  The Zs / partial products and the
  * lookup polynomials go into one commitment (prover.rs:237-241): concat, then p2hot_commit_cols(is_values = 1). */
 int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2hot_cols *b, p2hot_cols **out);
+
+/* ---------------------------------------------------------------- the standard gates' constraints (D = 2)
+ * evaluate_gate_constraints_base_batch (plonk/vanishing_poly.rs:702-728) on the quotient coset for eight gates of the reference.
+ * A gate of common_data.gates is described by
+ *   kind            P2HOT_GATE_*
+ *   row             its index in common_data.gates: the `row` compute_filter excludes (gates/gate.rs:326-333)
+ *   selector_index  selectors_info.selector_indices[row]; [group_first, group_end) = selectors_info.groups[selector_index]
+ *   param0          Constant: num_consts; Arithmetic / ArithmeticExtension / MulExtension: num_ops; BaseSum: num_limbs (<= 63)
+ *   param1          BaseSum: the base B (>= 2)
+ * and the set adds num_selectors = selectors_info.num_selectors(), num_lookup_selectors (4 + num_luts, or 0) and the public inputs
+ * hash.  At a point x_i the local wires / constants are row bitrev(i) of the wires / constants_sigmas commitments; with
+ * s = constants[selector_index]
+ *   filter_g = prod_{k in group, k != row} (k - s), times (0xFFFFFFFF - s) when num_selectors > 1      (gate.rs:326-333)
+ * the gate's own local_constants[c] is constants column num_selectors + num_lookup_selectors + c (gate.rs:179), and since every
+ * gate's constraints are added into one vector from index 0 (vanishing_poly.rs:722-725) and the reduction is linear
+ *   gate_sums[a][i] = sum_g filter_g(x_i) sum_j alpha_a^j c_{g,j}(x_i)                                  (canonical)
+ * Constraints c_{g,j}, in the reference's order:
+ *   NOOP            none (gates/noop.rs)
+ *   CONSTANT        constants[i] - wires[i], i < num_consts                                            (constant.rs:126-128)
+ *   PUBLIC_INPUT    wires[i] - public_inputs_hash[i], i < 4                                            (public_input.rs:108-112)
+ *   ARITHMETIC      w[4i+3] - (w[4i] w[4i+1] c0 + w[4i+2] c1)                                          (arithmetic_base.rs:173-184)
+ *   ARITHMETIC_EXT  per op the two base components of out - ((m0 m1) c0 + addend c1) in F[X]/(X^2 - 7); m0, m1, addend, out on
+ *                   wires 8i .. 8i+8                                                                   (arithmetic_extension.rs:92-110)
+ *   MUL_EXT         per op the two components of out - (m0 m1) c0; m0, m1, out on wires 6i .. 6i+6     (multiplication_extension.rs:86-101)
+ *   BASE_SUM        sum_k limb_k B^k - w[0], then per limb prod_{t < B} (limb - t); limbs on wires 1 ..  (base_sum.rs:153-170)
+ *   POSEIDON        the 123 constraints over 135 wires of PoseidonGate (poseidon.rs:204-283): swap (swap - 1), four deltas, the
+ *                   S-box inputs of full rounds 1..3, of the 22 partial rounds in their FAST form (hash/poseidon.rs:365-373,
+ *                   :415-441, :516-542), of the second four full rounds, and the 12 outputs; the state continues from the wire
+ *                   after every constrained S-box input
+ * Every other gate of the reference stays the caller's (the host gate_sums of the entry points below). */
+enum { P2HOT_GATE_NOOP, P2HOT_GATE_CONSTANT, P2HOT_GATE_PUBLIC_INPUT, P2HOT_GATE_ARITHMETIC,
+       P2HOT_GATE_ARITHMETIC_EXT, P2HOT_GATE_MUL_EXT, P2HOT_GATE_BASE_SUM, P2HOT_GATE_POSEIDON };
+typedef struct p2hot_gate { uint32_t kind, row, selector_index, group_first, group_end, param0, param1; } p2hot_gate;
+typedef struct p2hot_gate_set { const p2hot_gate *gates; uint32_t num_gates, num_selectors, num_lookup_selectors;
+                                uint64_t public_inputs_hash[4]; } p2hot_gate_set;
+/* The reduced gate sums alone: out_host HOST [num_challenges][n << log2_ceil(quotient_degree_factor)], natural order, canonical.
+ * wires / constants_sigmas as in p2hot_quotient_polys (any hasher); sigmas_first_col bounds the constants a gate may read.
+ * Raised before anything is enqueued -- P2HOT_EUNSUPPORTED: an unknown kind.  P2HOT_EINVAL: row outside its group (or a group of
+ * more than 256 gates), selector_index >= num_selectors, selectors + lookup selectors + the constants a gate reads beyond
+ * sigmas_first_col, a gate's wires beyond the wires commitment, B < 2 or num_limbs > 63, gates->gates null with num_gates > 0, a
+ * null set, commitments of another context, degree or rate, num_challenges outside 1..4. */
+int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                    const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,
+                    uint64_t *out_host);
+/* p2hot_quotient_polys / p2hot_quotient_polys_lookup with the gates of `gates` evaluated on the device: every argument keeps its
+ * meaning, and the host gate_sums (or NULL) is ADDED to the device-evaluated sums -- the residual of the gates the library does
+ * not know, evaluated by the caller (eval_filtered_base_batch, gate.rs:158-185).  Launch order: the gate kernels, the lookup
+ * kernel (if any) with their result as its gate sums, the permutation kernel.  Errors as p2hot_gate_sums and the extended entry
+ * point, before anything is enqueued; *chunks_out is NULL on failure. */
+int p2hot_quotient_polys_gates(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                               const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
+                               unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                               unsigned num_challenges, const uint64_t *const *gate_sums, const p2hot_gate_set *gates,
+                               uint64_t *values_out, p2hot_cols **chunks_out);
+int p2hot_quotient_polys_lookup_gates(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                      const p2hot_batch *zs_partial_products_lookups, const uint64_t *k_is, unsigned num_routed,
+                                      unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                      unsigned num_challenges, const uint64_t *const *gate_sums, unsigned num_lu_slots, unsigned num_lut_slots,
+                                      unsigned num_luts, size_t lookup_selectors_first_col, const uint64_t *deltas,
+                                      const uint64_t *lut_re_poly_evals, const p2hot_gate_set *gates, uint64_t *values_out,
+                                      p2hot_cols **chunks_out);
 
 /* ================================================================ multi-GPU: the coset-sharded commit
  * The rate-1/B LDE is B independent coset transforms and coset j is the contiguous row block bitrev(j) of the

@@ -71,7 +71,7 @@ use crate::plonk::circuit_builder::{LookupChallenges, NUM_COINS_LOOKUP};
 use crate::plonk::circuit_data::{CommonCircuitData, ProverOnlyCircuitData};
 use crate::plonk::config::{GenericConfig, GenericHashOut, Hasher};
 use crate::plonk::plonk_common::reduce_with_powers_multi;
-use crate::plonk::vanishing_poly::{evaluate_gate_constraints_base_batch, get_lut_poly};
+use crate::plonk::vanishing_poly::get_lut_poly;
 use crate::plonk::vars::EvaluationVarsBaseBatch;
 use crate::util::strided_view::PackedStridedView;
 use crate::util::{log2_ceil, log2_strict, reverse_bits};
@@ -164,6 +164,39 @@ pub struct P2hotFriProofLayout {
     pub initial_paths_words: usize,
     pub step_evals_words: usize,
     pub step_paths_words: usize,
+}
+
+/// P2HOT_GATE_*: the gate kinds the library evaluates on the device (include/p2hot.h)
+pub const P2HOT_GATE_NOOP: u32 = 0;
+pub const P2HOT_GATE_CONSTANT: u32 = 1;
+pub const P2HOT_GATE_PUBLIC_INPUT: u32 = 2;
+pub const P2HOT_GATE_ARITHMETIC: u32 = 3;
+pub const P2HOT_GATE_ARITHMETIC_EXT: u32 = 4;
+pub const P2HOT_GATE_MUL_EXT: u32 = 5;
+pub const P2HOT_GATE_BASE_SUM: u32 = 6;
+pub const P2HOT_GATE_POSEIDON: u32 = 7;
+
+/// p2hot_gate: one entry of common_data.gates (its index, its selector group, its parameters)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotGate {
+    pub kind: u32,
+    pub row: u32,
+    pub selector_index: u32,
+    pub group_first: u32,
+    pub group_end: u32,
+    pub param0: u32,
+    pub param1: u32,
+}
+
+/// p2hot_gate_set
+#[repr(C)]
+pub struct P2hotGateSet {
+    pub gates: *const P2hotGate,
+    pub num_gates: u32,
+    pub num_selectors: u32,
+    pub num_lookup_selectors: u32,
+    pub public_inputs_hash: [u64; 4],
 }
 
 /// p2hot_allgather_fn
@@ -353,6 +386,23 @@ extern "C" {
         chunks_out: *mut *mut P2hotCols,
     ) -> c_int;
     pub fn p2hot_cols_concat(ctx: *mut P2hotCtx, a: *const P2hotCols, b: *const P2hotCols, out: *mut *mut P2hotCols) -> c_int;
+    pub fn p2hot_gate_sums(
+        ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize, gates: *const P2hotGateSet,
+        quotient_degree_factor: c_uint, alphas: *const u64, num_challenges: c_uint, out_host: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_quotient_polys_gates(
+        ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize,
+        zs_partial_products: *const P2hotBatch, k_is: *const u64, num_routed: c_uint, quotient_degree_factor: c_uint, betas: *const u64,
+        gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gate_sums: *const *const u64, gates: *const P2hotGateSet,
+        values_out: *mut u64, chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
+    pub fn p2hot_quotient_polys_lookup_gates(
+        ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize,
+        zs_partial_products_lookups: *const P2hotBatch, k_is: *const u64, num_routed: c_uint, quotient_degree_factor: c_uint, betas: *const u64,
+        gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gate_sums: *const *const u64, num_lu_slots: c_uint, num_lut_slots: c_uint,
+        num_luts: c_uint, lookup_selectors_first_col: usize, deltas: *const u64, lut_re_poly_evals: *const u64, gates: *const P2hotGateSet,
+        values_out: *mut u64, chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
     // ---- multi-GPU
     pub fn p2hot_comm_unique_id(out: *mut u8) -> c_int;
     pub fn p2hot_comm_create_rccl(ctx: *mut P2hotCtx, rank: c_int, world: c_int, id: *const u8, out: *mut *mut P2hotComm) -> c_int;
@@ -1262,11 +1312,64 @@ pub fn eval_commitment<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>,
 // ------------------------------------------------------------------------------------------------
 // compute_quotient_polys (plonk/prover.rs:609-815): the permutation argument's share on the GPU
 // ------------------------------------------------------------------------------------------------
+/// The descriptor of a gate the library evaluates on the device (include/p2hot.h: Noop, Constant, PublicInput, Arithmetic,
+/// ArithmeticExtension, MulExtension, BaseSum<B>, Poseidon; D = 2), or `None` for every other gate.  The kind is read from the prefix
+/// of `id()` (the Debug form of the gate struct), the parameters from `num_constraints()` / `num_wires()`, BaseSum's base from the
+/// id's suffix (gates/base_sum.rs:55-57: "... + Base: B").
+fn gate_descriptor<F: RichField + Extendable<D>, const D: usize>(
+    id: &str,
+    num_constraints: usize,
+    num_wires: usize,
+    row: usize,
+    selector_index: usize,
+    group_first: usize,
+    group_end: usize,
+) -> Option<P2hotGate> {
+    if D != 2 {
+        return None;
+    }
+    let (kind, param0, param1) = if id.starts_with("NoopGate") {
+        (P2HOT_GATE_NOOP, 0, 0)
+    } else if id.starts_with("ConstantGate {") {
+        (P2HOT_GATE_CONSTANT, num_constraints, 0)
+    } else if id.starts_with("PublicInputGate") {
+        (P2HOT_GATE_PUBLIC_INPUT, 0, 0)
+    } else if id.starts_with("ArithmeticGate {") {
+        (P2HOT_GATE_ARITHMETIC, num_constraints, 0)
+    } else if id.starts_with("ArithmeticExtensionGate {") {
+        (P2HOT_GATE_ARITHMETIC_EXT, num_constraints / D, 0)
+    } else if id.starts_with("MulExtensionGate {") {
+        (P2HOT_GATE_MUL_EXT, num_constraints / D, 0)
+    } else if id.starts_with("BaseSumGate {") {
+        let base: usize = id.rsplit("Base: ").next()?.trim().parse().ok()?;
+        if base < 2 || num_wires == 0 || num_wires - 1 > 63 {
+            return None;
+        }
+        (P2HOT_GATE_BASE_SUM, num_wires - 1, base)
+    } else if id.starts_with("PoseidonGate(") && num_constraints == 123 && num_wires == 135 {
+        (P2HOT_GATE_POSEIDON, 0, 0)
+    } else {
+        return None;
+    };
+    Some(P2hotGate {
+        kind,
+        row: row as u32,
+        selector_index: selector_index as u32,
+        group_first: group_first as u32,
+        group_end: group_end as u32,
+        param0: param0 as u32,
+        param1: param1 as u32,
+    })
+}
+
 /// The vanishing polynomial's terms are `[L_0 (Z - 1) ..] ++ [partial product checks ..] ++ [gate constraint terms ..]`
-/// (plonk/vanishing_poly.rs:326-330) reduced with the powers of each alpha.  The gate terms are circuit specific: they are
-/// evaluated HERE by the reference's own `evaluate_gate_constraints_base_batch` on the reference's own point batches
-/// (prover.rs:684-779, BATCH_SIZE = 32) and reduced on their own; everything in front of them -- 80 routed wires x 2 challenges at
-/// 2^23 points for a 2^20-gate circuit -- and the division by Z_H, the coset_ifft and the trim run in ONE `p2hot_quotient_polys`
+/// (plonk/vanishing_poly.rs:326-330) reduced with the powers of each alpha.  The gate terms of the eight standard gates
+/// (`gate_descriptor`) are evaluated on the device by `p2hot_quotient_polys_gates` / `_lookup_gates`; every OTHER gate of the
+/// circuit is evaluated HERE by the reference's own `eval_filtered_base_batch` on the reference's own point batches
+/// (prover.rs:684-779, BATCH_SIZE = 32, added up as vanishing_poly.rs:702-728 does) and reduced into the residual `gate_sums` the
+/// library adds to its own -- a circuit without such a gate never reads the host copy of the leaf matrix (no fence, no loop, no
+/// upload).  Everything in front of the gate terms -- 80 routed wires x 2 challenges at
+/// 2^23 points for a 2^20-gate circuit -- and the division by Z_H, the coset_ifft and the trim run in the same
 /// call on the LDE matrices the three commitments already hold on the device.  Returns the reference's result (one polynomial of
 /// `quotient_degree_factor * n` coefficients per challenge); `None` sends the caller down the CPU body (a commitment without a
 /// device handle, more than 4 challenges).  A circuit with lookup tables takes `p2hot_quotient_polys_lookup`: the same call with the
@@ -1312,9 +1415,29 @@ pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, 
     let lde_size = n << quotient_degree_bits;
     let num_constants = common_data.constants_range().len();
     let num_wires = common_data.config.num_wires;
-    // gate_sums[a][i] = reduce_with_powers(gate constraint terms at point i, alpha_a)
+    // common_data.gates -> descriptors for the device; `unmapped` = the gates this shim evaluates itself
+    let num_selectors = common_data.selectors_info.num_selectors();
+    let mut descriptors: Vec<P2hotGate> = Vec::new();
+    let mut unmapped: Vec<usize> = Vec::new();
+    for (row, gate) in common_data.gates.iter().enumerate() {
+        let selector_index = common_data.selectors_info.selector_indices[row];
+        let group = common_data.selectors_info.groups[selector_index].clone();
+        match gate_descriptor::<F, D>(&gate.0.id(), gate.0.num_constraints(), gate.0.num_wires(), row, selector_index, group.start, group.end) {
+            Some(d) => descriptors.push(d),
+            None => unmapped.push(row),
+        }
+    }
+    let pih = public_inputs_hash.to_vec();
+    let gate_set = P2hotGateSet {
+        gates: descriptors.as_ptr(),
+        num_gates: descriptors.len() as u32,
+        num_selectors: num_selectors as u32,
+        num_lookup_selectors: common_data.num_lookup_selectors as u32,
+        public_inputs_hash: [pih[0].to_canonical_u64(), pih[1].to_canonical_u64(), pih[2].to_canonical_u64(), pih[3].to_canonical_u64()],
+    };
+    // residual gate_sums[a][i] = reduce_with_powers(the UNMAPPED gates' constraint terms at point i, alpha_a); none: no host work
     const BATCH_SIZE: usize = 32; // prover.rs:607
-    let indices: Vec<usize> = (0..lde_size).collect();
+    let indices: Vec<usize> = if unmapped.is_empty() { Vec::new() } else { (0..lde_size).collect() };
     let per_point: Vec<F> = indices // point-major: [lde_size][nc]
         .par_chunks(BATCH_SIZE)
         .flat_map(|batch| {
@@ -1332,7 +1455,22 @@ pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, 
                 }
             }
             let vars_batch = EvaluationVarsBaseBatch::new(m, &local_constants_batch, &local_wires_batch, public_inputs_hash);
-            let constraint_terms_batch = evaluate_gate_constraints_base_batch::<F, D>(common_data, vars_batch);
+            // evaluate_gate_constraints_base_batch (vanishing_poly.rs:702-728) over the unmapped gates only
+            let mut constraint_terms_batch = vec![F::ZERO; common_data.num_gate_constraints * m];
+            for &row in &unmapped {
+                let selector_index = common_data.selectors_info.selector_indices[row];
+                let gate_constraints_batch = common_data.gates[row].0.eval_filtered_base_batch(
+                    vars_batch,
+                    row,
+                    selector_index,
+                    common_data.selectors_info.groups[selector_index].clone(),
+                    num_selectors,
+                    common_data.num_lookup_selectors,
+                );
+                for (acc, &v) in constraint_terms_batch.iter_mut().zip(gate_constraints_batch.iter()) {
+                    *acc += v;
+                }
+            }
             let mut sums = vec![F::ZERO; m * nc];
             if !constraint_terms_batch.is_empty() {
                 for j in 0..m {
@@ -1345,6 +1483,7 @@ pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, 
         .collect();
     let gate_sums: Vec<Vec<u64>> = (0..nc).map(|a| per_point.iter().skip(a).step_by(nc).map(|v| v.to_canonical_u64()).collect()).collect();
     let gate_ptrs: Vec<*const u64> = gate_sums.iter().map(|v| v.as_ptr()).collect();
+    let residual: *const *const u64 = if unmapped.is_empty() { core::ptr::null() } else { gate_ptrs.as_ptr() };
     let num_routed = common_data.config.num_routed_wires;
     let k_is: Vec<u64> = common_data.k_is[..num_routed].iter().map(|k| k.to_canonical_u64()).collect();
     let to_u64 = |v: &[F]| -> Vec<u64> { v.iter().map(|x| x.to_canonical_u64()).collect() };
@@ -1376,22 +1515,22 @@ pub fn compute_quotient_polys<F: RichField + Extendable<D>, C: GenericConfig<D, 
             let mut chunks = ColsGuard(core::ptr::null_mut()); // freed on every path, the panicking ones included
             let rc = if has_lookup {
                 unsafe {
-                    p2hot_quotient_polys_lookup(
+                    p2hot_quotient_polys_lookup_gates(
                         ctx, h_wires, h_cs, common_data.sigmas_range().start, h_zs, k_is.as_ptr(), num_routed as c_uint, qdf as c_uint,
-                        b.as_ptr(), g.as_ptr(), a.as_ptr(), nc as c_uint, gate_ptrs.as_ptr(), num_lu_slots as c_uint, num_lut_slots as c_uint,
-                        num_luts as c_uint, common_data.selectors_info.num_selectors(), d.as_ptr(), lut_re_poly_evals.as_ptr(),
+                        b.as_ptr(), g.as_ptr(), a.as_ptr(), nc as c_uint, residual, num_lu_slots as c_uint, num_lut_slots as c_uint,
+                        num_luts as c_uint, num_selectors, d.as_ptr(), lut_re_poly_evals.as_ptr(), &gate_set,
                         core::ptr::null_mut(), &mut chunks.0,
                     )
                 }
             } else {
                 unsafe {
-                    p2hot_quotient_polys(
+                    p2hot_quotient_polys_gates(
                         ctx, h_wires, h_cs, common_data.sigmas_range().start, h_zs, k_is.as_ptr(), num_routed as c_uint, qdf as c_uint,
-                        b.as_ptr(), g.as_ptr(), a.as_ptr(), nc as c_uint, gate_ptrs.as_ptr(), core::ptr::null_mut(), &mut chunks.0,
+                        b.as_ptr(), g.as_ptr(), a.as_ptr(), nc as c_uint, residual, &gate_set, core::ptr::null_mut(), &mut chunks.0,
                     )
                 }
             };
-            check(ctx, rc, "p2hot_quotient_polys"); // "Quotient has failed ..." panics here as trim_to_len does on the CPU path
+            check(ctx, rc, "p2hot_quotient_polys_gates"); // "Quotient has failed ..." panics here as trim_to_len does on the CPU path
             check(ctx, unsafe { p2hot_cols_download(chunks.0, 0, nc * qdf, out) }, "p2hot_cols_download");
         })
     });

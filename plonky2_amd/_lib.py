@@ -142,6 +142,10 @@ SIGNATURES = {
     "p2hot_quotient_polys_lookup": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), u, u, u, sz, vp, vp, vp,
                                         C.POINTER(vp)]),
     "p2hot_cols_concat": (i, [vp, vp, vp, C.POINTER(vp)]),
+    "p2hot_gate_sums": (i, [vp, vp, vp, sz, vp, u, vp, u, vp]),
+    "p2hot_quotient_polys_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), vp, vp, C.POINTER(vp)]),
+    "p2hot_quotient_polys_lookup_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), u, u, u, sz, vp, vp, vp, vp,
+                                              C.POINTER(vp)]),
     "p2hot_comm_unique_id": (i, [vp]),
     "p2hot_comm_create_rccl": (i, [vp, i, i, vp, C.POINTER(vp)]),
     "p2hot_comm_create_callback": (i, [vp, i, i, ALLGATHER_FN, vp, C.POINTER(vp)]),

@@ -1375,11 +1375,130 @@ extern "C" int p2hot_quotient_chunks(p2hot_ctx *ctx, const uint64_t *const *quot
     return quotient_chunks_core(ctx, d_work, num_challenges, degree_bits, qbits, quotient_degree_factor, "quotient_chunks", chunks_out);
 }
 
+// ------------------------------------------------------------------ the standard gates' constraints (gates.hpp; include/p2hot.h)
+// every check of a gate set, before anything is enqueued; *max_constraints = the longest constraint list (the alpha-power table's length)
+static int gates_validate(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
+                          size_t sigmas_first_col, const char *what, unsigned *max_constraints) {
+    *max_constraints = 1;
+    if (!gs) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null gate set", what);
+    if (gs->num_gates && !gs->gates) P2_FAIL(ctx, P2HOT_EINVAL, "%s: %u gates but a null descriptor array", what, gs->num_gates);
+    if (sigmas_first_col > constants_sigmas->W) P2_FAIL(ctx, P2HOT_EINVAL, "%s: sigmas_first_col beyond the constants_sigmas commitment", what);
+    for (unsigned k = 0; k < gs->num_gates; ++k) {
+        const p2hot_gate &g = gs->gates[k];
+        if (g.kind > P2HOT_GATE_POSEIDON) P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: gate %u has the unknown kind %u", what, k, g.kind);
+        if (g.row < g.group_first || g.row >= g.group_end) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: row %u outside its group [%u, %u)", what, k, g.row, g.group_first, g.group_end);
+        if (g.group_end - g.group_first > 256) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: a selector group of %u gates (at most 256)", what, k, g.group_end - g.group_first);
+        if (g.selector_index >= gs->num_selectors) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: selector %u of %u", what, k, g.selector_index, gs->num_selectors);
+        if (g.kind == P2HOT_GATE_BASE_SUM && (g.param1 < 2 || g.param0 > 63)) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: BaseSum base %u, %u limbs (B >= 2, at most 63 limbs)", what, k, g.param1, g.param0);
+        if (g.param0 > (1u << 24)) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: parameter %u", what, k, g.param0);
+        unsigned nw, nk, ncons;
+        gates::shape(g, nw, nk, ncons);
+        if (nw > wires->W) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u reads %u wires of %zu", what, k, nw, wires->W);
+        if ((size_t)gs->num_selectors + gs->num_lookup_selectors + nk > sigmas_first_col)
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: %u selectors, %u lookup selectors and %u constants reach past sigmas_first_col = %zu", what, k,
+                    gs->num_selectors, gs->num_lookup_selectors, nk, sigmas_first_col);
+        if (ncons > *max_constraints) *max_constraints = ncons;
+    }
+    return P2HOT_OK;
+}
+
+// apow HOST [nc][stride]: alpha_a^j, canonical
+static void gates_alpha_powers(u64 *apow, const uint64_t *alphas, unsigned nc, unsigned stride) {
+    for (unsigned a = 0; a < nc; ++a) {
+        u64 pw = 1;
+        for (unsigned j = 0; j < stride; ++j, pw = gl::mul(pw, alphas[a])) apow[(size_t)a * stride + j] = gl::canon(pw);
+    }
+}
+
+// the launches: the cheap kinds MAX_CHEAP descriptors at a time, then one launch per PoseidonGate; all add into d_out [nc][1 << log_nq]
+static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
+                        const u64 *d_apow, unsigned apow_stride, u64 *d_out, unsigned log_nq, unsigned nc) {
+    const size_t m = (size_t)1 << log_nq;
+    const dim3 grid(cdiv(m, 256)), block(256);
+    gates::Args a{};
+    a.wires = wires->d_lde, a.wires_stride = wires->col_stride_lde();
+    a.consts = constants_sigmas->d_lde, a.consts_stride = constants_sigmas->col_stride_lde();
+    a.apow = d_apow, a.apow_stride = apow_stride, a.out = d_out, a.log_nq = log_nq;
+    a.num_selectors = gs->num_selectors, a.consts_first = gs->num_selectors + gs->num_lookup_selectors;
+    for (unsigned k = 0; k < 4; ++k) a.pih[k] = gl::canon(gs->public_inputs_hash[k]);
+    auto flush = [&]() -> int {
+        if (!a.num_gates) return P2HOT_OK;
+        ProfScope prof(ctx, "gates_cheap");
+        switch (nc) {
+            case 1: P2HOT_LAUNCH((gates::cheap_gates_kernel<1>), grid, block, 0, ctx->stream, a); break;
+            case 2: P2HOT_LAUNCH((gates::cheap_gates_kernel<2>), grid, block, 0, ctx->stream, a); break;
+            case 3: P2HOT_LAUNCH((gates::cheap_gates_kernel<3>), grid, block, 0, ctx->stream, a); break;
+            default: P2HOT_LAUNCH((gates::cheap_gates_kernel<4>), grid, block, 0, ctx->stream, a); break;
+        }
+        P2_LAUNCH_CHECK(ctx);
+        a.num_gates = 0;
+        return P2HOT_OK;
+    };
+    for (unsigned k = 0; k < gs->num_gates; ++k) {
+        const p2hot_gate &g = gs->gates[k];
+        if (g.kind == P2HOT_GATE_NOOP || g.kind == P2HOT_GATE_POSEIDON) continue;
+        a.gates[a.num_gates++] = g;
+        if (a.num_gates == gates::MAX_CHEAP) P2_TRY(flush());
+    }
+    P2_TRY(flush());
+    for (unsigned k = 0; k < gs->num_gates; ++k) {
+        if (gs->gates[k].kind != P2HOT_GATE_POSEIDON) continue;
+        gates::PoseidonArgs pa{};
+        pa.wires = a.wires, pa.wires_stride = a.wires_stride, pa.consts = a.consts, pa.consts_stride = a.consts_stride;
+        pa.apow = d_apow, pa.apow_stride = apow_stride, pa.out = d_out, pa.log_nq = log_nq, pa.num_selectors = gs->num_selectors;
+        pa.gate = gs->gates[k];
+        ProfScope prof(ctx, "gates_poseidon");
+        switch (nc) {
+            case 1: P2HOT_LAUNCH((gates::poseidon_gate_kernel<1>), grid, block, 0, ctx->stream, pa); break;
+            case 2: P2HOT_LAUNCH((gates::poseidon_gate_kernel<2>), grid, block, 0, ctx->stream, pa); break;
+            case 3: P2HOT_LAUNCH((gates::poseidon_gate_kernel<3>), grid, block, 0, ctx->stream, pa); break;
+            default: P2HOT_LAUNCH((gates::poseidon_gate_kernel<4>), grid, block, 0, ctx->stream, pa); break;
+        }
+        P2_LAUNCH_CHECK(ctx);
+    }
+    return P2HOT_OK;
+}
+
+// the reduced gate sums on their own (include/p2hot.h): evaluate_gate_constraints_base_batch (plonk/vanishing_poly.rs:702-728) for
+// the gates of the set, reduced by the powers of every alpha
+extern "C" int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                               const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,
+                               uint64_t *out_host) {
+    P2_ENTER(ctx);
+    if (!wires || !constants_sigmas || !alphas || !out_host) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: null argument");
+    if (wires->ctx != ctx || constants_sigmas->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: a commitment belongs to another context");
+    if (constants_sigmas->log_n != wires->log_n || constants_sigmas->rate_bits != wires->rate_bits)
+        P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: the commitments differ in degree or rate");
+    if (num_challenges == 0 || num_challenges > 4) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: %u challenges (1..4)", num_challenges);
+    if (quotient_degree_factor < 2) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: bad quotient degree factor");
+    unsigned qbits = 0;
+    while ((1u << qbits) < quotient_degree_factor) ++qbits;
+    if (qbits > wires->rate_bits) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: quotient degree 2^%u above the rate 2^%u (prover.rs:632-636)", qbits, wires->rate_bits);
+    unsigned stride = 1;
+    P2_TRY(gates_validate(ctx, gates, wires, constants_sigmas, sigmas_first_col, "gate_sums", &stride));
+    const unsigned log_nq = wires->log_n + qbits;
+    const size_t m = (size_t)1 << log_nq;
+    PoolBuf d_out(ctx), d_apow(ctx);
+    P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8, &d_out.p));
+    P2_TRY(pool_alloc(ctx, (size_t)num_challenges * stride * 8, &d_apow.p));
+    std::vector<u64> apow((size_t)num_challenges * stride);
+    gates_alpha_powers(apow.data(), alphas, num_challenges, stride);
+    auto body = [&]() -> int {
+        P2_HIP(ctx, hipMemcpyAsync(d_apow.p, apow.data(), apow.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        P2_HIP(ctx, hipMemsetAsync(d_out.p, 0, (size_t)num_challenges * m * 8, ctx->stream));
+        P2_TRY(gates_launch(ctx, gates, wires, constants_sigmas, d_apow.u(), stride, d_out.u(), log_nq, num_challenges));
+        P2_HIP(ctx, hipMemcpyAsync(out_host, d_out.p, (size_t)num_challenges * m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return P2HOT_OK;
+    };
+    return sync_checked(ctx, body(), "gate_sums");
+}
+
 // compute_quotient_polys (plonky2/src/plonk/prover.rs:609-815) without its gate evaluation: the permutation argument's vanishing
 // terms on the quotient coset (plonk/vanishing_poly.rs:167-330; kernel: plonk::quotient_perm_kernel) from the three commitments'
 // device-resident LDE matrices, plus the caller's reduced gate terms, over Z_H; then the same tail as p2hot_quotient_chunks.
 // `lk` (p2hot_quotient_polys_lookup): the lookup argument's terms (lookup::lookup_terms_kernel) go between the permutation terms and
-// the gate terms; null = p2hot_quotient_polys
+// the gate terms; null = p2hot_quotient_polys.  `gs` (p2hot_quotient_polys_gates / _lookup_gates): the set's gates are evaluated on the
+// device (gates.hpp) into the gate-sum buffer, on top of the caller's gate_sums, in front of both; null = none
 struct LookupQuot {
     unsigned num_lu_slots, num_lut_slots, num_luts;
     size_t selectors_first_col;
@@ -1389,7 +1508,7 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
                                const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
                                unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
                                unsigned num_challenges, const uint64_t *const *gate_sums, uint64_t *values_out, p2hot_cols **chunks_out,
-                               const LookupQuot *lk) {
+                               const LookupQuot *lk, const p2hot_gate_set *gs = nullptr, bool with_gates = false) {
     P2_ENTER(ctx);
     if (chunks_out) *chunks_out = nullptr;
     if (!wires || !constants_sigmas || !zs_partial_products || !k_is || !betas || !gammas || !alphas) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys: null argument");
@@ -1430,14 +1549,18 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
         if (lk->selectors_first_col > constants_sigmas->W || (size_t)4 + lk->num_luts > constants_sigmas->W - lk->selectors_first_col)
             P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: the lookup selectors do not fit the constants_sigmas commitment");
     }
+    unsigned gs_stride = 0;
+    if (with_gates) P2_TRY(gates_validate(ctx, gs, wires, constants_sigmas, sigmas_first_col, "quotient_polys_gates", &gs_stride));
     const size_t n_apow = lk ? (size_t)num_challenges * ((size_t)num_challenges * lk_Kc + 1) : 0, n_evals = lk ? (size_t)num_challenges * lk->num_luts : 0;
+    const size_t n_gpow = (size_t)num_challenges * gs_stride;
     PoolBuf d_work(ctx), d_small(ctx), d_gate(ctx);
     P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8 + 8, &d_work.p));
     const size_t nbk = (size_t)num_challenges * num_routed;
-    P2_TRY(pool_alloc(ctx, (nbk + 2 * rate + n_apow + n_evals) * 8, &d_small.p));
-    if (gate_sums || lk) P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8, &d_gate.p));
+    P2_TRY(pool_alloc(ctx, (nbk + 2 * rate + n_apow + n_evals + n_gpow) * 8, &d_small.p));
+    if (gate_sums || lk || with_gates) P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8, &d_gate.p));
     // ZeroPolyOnCoset::new(degree_bits, qbits) (field/src/zero_poly_coset.rs:21-34) and beta_c * k_j, on the host
-    std::vector<u64> small(nbk + 2 * rate + n_apow + n_evals);
+    std::vector<u64> small(nbk + 2 * rate + n_apow + n_evals + n_gpow);
+    if (with_gates) gates_alpha_powers(small.data() + nbk + 2 * rate + n_apow + n_evals, alphas, num_challenges, gs_stride);
     for (unsigned c = 0; c < num_challenges; ++c)
         for (unsigned j = 0; j < num_routed; ++j) small[(size_t)c * num_routed + j] = gl::canon(gl::mul(betas[c], k_is[j]));
     const size_t num_routed_ = nbk;  // (offset of the Z_H table behind the beta * k table)
@@ -1466,7 +1589,7 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
     q.sigmas = constants_sigmas->d_lde + sigmas_first_col * constants_sigmas->col_stride_lde(), q.sigmas_stride = constants_sigmas->col_stride_lde();
     q.zs = zs_partial_products->d_lde, q.zs_stride = zs_partial_products->col_stride_lde();
     q.bk = d_small.u(), q.zh = d_small.u() + nbk, q.inv_nx1 = inv_it->second;
-    q.gate_sums = gate_sums || lk ? d_gate.u() : nullptr;
+    q.gate_sums = gate_sums || lk || with_gates ? d_gate.u() : nullptr;
     q.out = d_work.u();
     q.num_routed = num_routed, q.degree = quotient_degree_factor, q.num_chunks = num_chunks, q.log_nq = log_nq, q.qbits = qbits;
     const u64 K = (u64)num_challenges + (u64)num_challenges * num_chunks;
@@ -1490,7 +1613,7 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
         lt.lz_stride = zs_partial_products->col_stride_lde();
         lt.lz = zs_partial_products->d_lde + (size_t)num_challenges * (1 + num_prods) * lt.lz_stride;
         lt.apow = d_small.u() + nbk + 2 * rate, lt.lut_evals = lt.apow + n_apow;
-        lt.gate_sums = gate_sums ? d_gate.u() : nullptr, lt.out = d_gate.u();
+        lt.gate_sums = gate_sums || with_gates ? d_gate.u() : nullptr, lt.out = d_gate.u();
         lt.num_lu_slots = lk->num_lu_slots, lt.num_lut_slots = lk->num_lut_slots, lt.lu_degree = quotient_degree_factor - 1;
         lt.S = lk_S, lt.lut_degree = (lk->num_lut_slots + lk_S - 1) / lk_S, lt.num_luts = lk->num_luts, lt.log_nq = log_nq, lt.qbits = qbits;
         for (unsigned c = 0; c < num_challenges; ++c)
@@ -1500,6 +1623,10 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
         P2_HIP(ctx, hipMemcpyAsync(d_small.p, small.data(), small.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         for (unsigned c = 0; c < num_challenges && gate_sums; ++c)
             P2_HIP(ctx, hipMemcpyAsync(d_gate.u() + (size_t)c * m, gate_sums[c], m * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (with_gates) {  // on top of the caller's residual sums (or of zeros)
+            if (!gate_sums) P2_HIP(ctx, hipMemsetAsync(d_gate.p, 0, (size_t)num_challenges * m * 8, ctx->stream));
+            P2_TRY(gates_launch(ctx, gs, wires, constants_sigmas, d_small.u() + nbk + 2 * rate + n_apow + n_evals, gs_stride, d_gate.u(), log_nq, num_challenges));
+        }
         if (lk) {
             ProfScope prof(ctx, "quotient_lookup");
             const dim3 grid(cdiv(m, 256)), block(256);
@@ -1551,6 +1678,29 @@ extern "C" int p2hot_quotient_polys_lookup(p2hot_ctx *ctx, const p2hot_batch *wi
     const LookupQuot lk{num_lu_slots, num_lut_slots, num_luts, lookup_selectors_first_col, deltas, lut_re_poly_evals};
     return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products_lookups, k_is, num_routed, quotient_degree_factor,
                                betas, gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, &lk);
+}
+
+// p2hot_quotient_polys / p2hot_quotient_polys_lookup with evaluate_gate_constraints_base_batch (plonk/vanishing_poly.rs:702-728) for
+// the gates of the set on the device; the host gate_sums is the residual of every other gate
+extern "C" int p2hot_quotient_polys_gates(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                          const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
+                                          unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                          unsigned num_challenges, const uint64_t *const *gate_sums, const p2hot_gate_set *gates,
+                                          uint64_t *values_out, p2hot_cols **chunks_out) {
+    return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products, k_is, num_routed, quotient_degree_factor, betas,
+                               gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, nullptr, gates, true);
+}
+
+extern "C" int p2hot_quotient_polys_lookup_gates(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                                 const p2hot_batch *zs_partial_products_lookups, const uint64_t *k_is, unsigned num_routed,
+                                                 unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas,
+                                                 const uint64_t *alphas, unsigned num_challenges, const uint64_t *const *gate_sums,
+                                                 unsigned num_lu_slots, unsigned num_lut_slots, unsigned num_luts, size_t lookup_selectors_first_col,
+                                                 const uint64_t *deltas, const uint64_t *lut_re_poly_evals, const p2hot_gate_set *gates,
+                                                 uint64_t *values_out, p2hot_cols **chunks_out) {
+    const LookupQuot lk{num_lu_slots, num_lut_slots, num_luts, lookup_selectors_first_col, deltas, lut_re_poly_evals};
+    return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products_lookups, k_is, num_routed, quotient_degree_factor,
+                               betas, gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, &lk, gates, true);
 }
 
 // ------------------------------------------------------------------ lookup polynomials (plonk/prover.rs:451-605)

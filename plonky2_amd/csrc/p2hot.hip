@@ -1,5 +1,5 @@
 // p2hot.hip -- context, pass planning and the C ABI of libp2hot (see include/p2hot.h).
-// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp.
+// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / gates.hpp.
 #include "../../include/p2hot.h"
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "fri.hpp"
 #include "plonk.hpp"
 #include "lookup.hpp"
+#include "gates.hpp"
 #include "merkle.hpp"
 #include "keccak.hpp"
 #include "ntt.hpp"

@@ -224,3 +224,114 @@ def compute_quotient_polys_lookup(wires_commitment, constants_sigmas_commitment,
     eng.check(rc)
     cols = DeviceColumns(eng, h)
     return (cols, vals) if want_values else cols
+
+
+# ------------------------------------------------------------------ the standard gates' constraints
+GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_MUL_EXT, GATE_BASE_SUM, GATE_POSEIDON = range(8)
+
+
+class _P2hotGate(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("kind", "row", "selector_index", "group_first", "group_end", "param0", "param1")]
+
+
+class _P2hotGateSet(C.Structure):
+    _fields_ = [("gates", C.POINTER(_P2hotGate)), ("num_gates", C.c_uint32), ("num_selectors", C.c_uint32),
+                ("num_lookup_selectors", C.c_uint32), ("public_inputs_hash", C.c_uint64 * 4)]
+
+
+class GateSet:
+    """p2hot_gate_set (include/p2hot.h): the gates of common_data.gates the library evaluates on the device.
+
+    gates: (kind, row, selector_index, group_first, group_end, param0, param1) per gate -- row = the gate's index in
+    common_data.gates, [group_first, group_end) = selectors_info.groups[selector_index], param0 = num_consts / num_ops /
+    num_limbs, param1 = BaseSum's base; num_selectors = selectors_info.num_selectors(); num_lookup_selectors = 4 + num_luts of
+    a circuit with lookup tables, else 0; public_inputs_hash: four field elements."""
+
+    def __init__(self, gates, num_selectors, num_lookup_selectors=0, public_inputs_hash=(0, 0, 0, 0)):
+        gates = [tuple(int(v) for v in g) for g in gates]
+        if any(len(g) != 7 for g in gates) or len(public_inputs_hash) != 4:
+            raise ValueError("a gate is (kind, row, selector_index, group_first, group_end, param0, param1); the hash has 4 words")
+        self._array = (_P2hotGate * max(len(gates), 1))(*[_P2hotGate(*g) for g in gates])
+        self._set = _P2hotGateSet(C.cast(self._array, C.POINTER(_P2hotGate)), len(gates), num_selectors, num_lookup_selectors,
+                                  (C.c_uint64 * 4)(*[int(v) for v in public_inputs_hash]))
+        self.gates = gates
+
+    @property
+    def ptr(self):
+        return C.cast(C.pointer(self._set), C.c_void_p)
+
+
+def gate_sums(wires_commitment, constants_sigmas_commitment, sigmas_first_col, gate_set, quotient_degree_factor, alphas, engine=None):
+    """evaluate_gate_constraints_base_batch (vanishing_poly.rs:702-728) for the gates of `gate_set` on the quotient coset, reduced
+    by the powers of every alpha -- one p2hot_gate_sums call.  Returns [num_challenges][n << qbits], natural order, canonical."""
+    eng = engine or wires_commitment.engine
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.uint64))
+    qb = max(0, (quotient_degree_factor - 1).bit_length())
+    out = np.zeros((len(a), (1 << wires_commitment.degree_log) << qb), dtype=np.uint64)
+    eng.check(eng.lib.p2hot_gate_sums(eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, gate_set.ptr,
+                                      quotient_degree_factor, a.ctypes.data_as(C.c_void_p), len(a), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def _quotient_call(eng, call, nc, m, want_values):
+    vals = np.zeros((nc, m), dtype=np.uint64) if want_values else None
+    h = C.c_void_p()
+    rc = call(vals.ctypes.data_as(C.c_void_p) if want_values else None, C.byref(h))
+    if rc == 1 and b"Quotient has failed" in eng.lib.p2hot_last_error(eng._ctx):
+        raise ValueError(eng.lib.p2hot_last_error(eng._ctx).decode())  # the reference panics (polynomial/mod.rs:164-178)
+    eng.check(rc)
+    from ..fri.oracle import DeviceColumns
+    cols = DeviceColumns(eng, h)
+    return (cols, vals) if want_values else cols
+
+
+def _host_gate_sums(gate_sums, nc, m):
+    if gate_sums is None:
+        return None, None
+    gs = np.ascontiguousarray(np.asarray(gate_sums, dtype=np.uint64))
+    if gs.shape != (nc, m):
+        raise ValueError("gate_sums must be [num_challenges][n << ceil(log2(quotient_degree_factor))]")
+    return gs, (C.c_void_p * max(nc, 1))(*[gs[c].ctypes.data for c in range(nc)])
+
+
+def compute_quotient_polys_gates(wires_commitment, constants_sigmas_commitment, sigmas_first_col, zs_partial_products_commitment, k_is,
+                                 quotient_degree_factor, betas, gammas, alphas, gate_set, gate_sums=None, want_values=False, engine=None):
+    """compute_quotient_polys above with the gates of `gate_set` evaluated on the device (one p2hot_quotient_polys_gates call);
+    `gate_sums`, if given, is the caller's residual of the other gates and is added to the device's sums."""
+    eng = engine or wires_commitment.engine
+    k = np.ascontiguousarray(np.asarray(k_is, dtype=np.uint64))
+    b, g, a = (np.ascontiguousarray(np.asarray(v, dtype=np.uint64)) for v in (betas, gammas, alphas))
+    if not (b.shape == g.shape == a.shape and b.ndim == 1):
+        raise ValueError("betas, gammas and alphas must be equally long vectors")
+    nc = len(b)
+    m = (1 << wires_commitment.degree_log) << max(0, (quotient_degree_factor - 1).bit_length())
+    gs, gptrs = _host_gate_sums(gate_sums, nc, m)
+    return _quotient_call(eng, lambda vals, h: eng.lib.p2hot_quotient_polys_gates(
+        eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, zs_partial_products_commitment._h,
+        k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+        a.ctypes.data_as(C.c_void_p), nc, gptrs, gate_set.ptr, vals, h), nc, m, want_values)
+
+
+def compute_quotient_polys_lookup_gates(wires_commitment, constants_sigmas_commitment, sigmas_first_col,
+                                        zs_partial_products_lookups_commitment, k_is, quotient_degree_factor, betas, gammas, alphas,
+                                        num_lu_slots, num_lut_slots, lookup_selectors_first_col, deltas, lut_re_poly_evals, gate_set,
+                                        gate_sums=None, want_values=False, engine=None):
+    """compute_quotient_polys_lookup above with the gates of `gate_set` evaluated on the device (one
+    p2hot_quotient_polys_lookup_gates call); `gate_sums` is the caller's residual of the other gates."""
+    eng = engine or wires_commitment.engine
+    k = np.ascontiguousarray(np.asarray(k_is, dtype=np.uint64))
+    b, g, a = (np.ascontiguousarray(np.asarray(v, dtype=np.uint64)) for v in (betas, gammas, alphas))
+    if not (b.shape == g.shape == a.shape and b.ndim == 1):
+        raise ValueError("betas, gammas and alphas must be equally long vectors")
+    nc = len(b)
+    d = np.ascontiguousarray(np.asarray(deltas, dtype=np.uint64))
+    ev = np.ascontiguousarray(np.asarray(lut_re_poly_evals, dtype=np.uint64).reshape(nc, -1))
+    if d.shape != (nc, 4):
+        raise ValueError("deltas must be [num_challenges][4]")
+    m = (1 << wires_commitment.degree_log) << max(0, (quotient_degree_factor - 1).bit_length())
+    gs, gptrs = _host_gate_sums(gate_sums, nc, m)
+    return _quotient_call(eng, lambda vals, h: eng.lib.p2hot_quotient_polys_lookup_gates(
+        eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, zs_partial_products_lookups_commitment._h,
+        k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+        a.ctypes.data_as(C.c_void_p), nc, gptrs, num_lu_slots, num_lut_slots, ev.shape[1], lookup_selectors_first_col,
+        d.ctypes.data_as(C.c_void_p), ev.ctypes.data_as(C.c_void_p), gate_set.ptr, vals, h), nc, m, want_values)
