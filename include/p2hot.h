@@ -575,7 +575,8 @@ int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2hot_cols *b, 
  *   row             its index in common_data.gates: the `row` compute_filter excludes (gates/gate.rs:326-333)
  *   selector_index  selectors_info.selector_indices[row]; [group_first, group_end) = selectors_info.groups[selector_index]
  *   param0          Constant: num_consts; Arithmetic / ArithmeticExtension / MulExtension: num_ops; BaseSum: num_limbs (<= 63)
- *   param1          BaseSum: the base B (>= 2)
+ *   param1          BaseSum: the base B, 2 <= B <= quotient_degree_factor: the range constraint of a limb has degree B, and a
+ *                   circuit holds a gate only if group size + degree <= quotient degree factor + 1 (gates/selectors.rs:101-160)
  * and the set adds num_selectors = selectors_info.num_selectors(), num_lookup_selectors (4 + num_luts, or 0) and the public inputs
  * hash.  At a point x_i the local wires / constants are row bitrev(i) of the wires / constants_sigmas commitments; with
  * s = constants[selector_index]
@@ -606,7 +607,7 @@ typedef struct p2hot_gate_set { const p2hot_gate *gates; uint32_t num_gates, num
  * wires / constants_sigmas as in p2hot_quotient_polys (any hasher); sigmas_first_col bounds the constants a gate may read.
  * Raised before anything is enqueued -- P2HOT_EUNSUPPORTED: an unknown kind.  P2HOT_EINVAL: row outside its group (or a group of
  * more than 256 gates), selector_index >= num_selectors, selectors + lookup selectors + the constants a gate reads beyond
- * sigmas_first_col, a gate's wires beyond the wires commitment, B < 2 or num_limbs > 63, gates->gates null with num_gates > 0, a
+ * sigmas_first_col, a gate's wires beyond the wires commitment, B < 2, B > quotient_degree_factor or num_limbs > 63, gates->gates null with num_gates > 0, a
  * null set, commitments of another context, degree or rate, num_challenges outside 1..4. */
 int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
                     const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,

@@ -1378,7 +1378,7 @@ extern "C" int p2hot_quotient_chunks(p2hot_ctx *ctx, const uint64_t *const *quot
 // ------------------------------------------------------------------ the standard gates' constraints (gates.hpp; include/p2hot.h)
 // every check of a gate set, before anything is enqueued; *max_constraints = the longest constraint list (the alpha-power table's length)
 static int gates_validate(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
-                          size_t sigmas_first_col, const char *what, unsigned *max_constraints) {
+                          size_t sigmas_first_col, unsigned quotient_degree_factor, const char *what, unsigned *max_constraints) {
     *max_constraints = 1;
     if (!gs) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null gate set", what);
     if (gs->num_gates && !gs->gates) P2_FAIL(ctx, P2HOT_EINVAL, "%s: %u gates but a null descriptor array", what, gs->num_gates);
@@ -1390,6 +1390,10 @@ static int gates_validate(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_
         if (g.group_end - g.group_first > 256) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: a selector group of %u gates (at most 256)", what, k, g.group_end - g.group_first);
         if (g.selector_index >= gs->num_selectors) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: selector %u of %u", what, k, g.selector_index, gs->num_selectors);
         if (g.kind == P2HOT_GATE_BASE_SUM && (g.param1 < 2 || g.param0 > 63)) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: BaseSum base %u, %u limbs (B >= 2, at most 63 limbs)", what, k, g.param1, g.param0);
+        // the range constraint has degree B and the kernel takes B - 1 products per limb: a circuit whose quotient degree factor is
+        // below B cannot hold the gate (gates/selectors.rs:101-160: group size + degree <= factor + 1)
+        if (g.kind == P2HOT_GATE_BASE_SUM && g.param1 > quotient_degree_factor)
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: BaseSum base %u above the quotient degree factor %u", what, k, g.param1, quotient_degree_factor);
         if (g.param0 > (1u << 24)) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: parameter %u", what, k, g.param0);
         unsigned nw, nk, ncons;
         gates::shape(g, nw, nk, ncons);
@@ -1475,7 +1479,7 @@ extern "C" int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p
     while ((1u << qbits) < quotient_degree_factor) ++qbits;
     if (qbits > wires->rate_bits) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: quotient degree 2^%u above the rate 2^%u (prover.rs:632-636)", qbits, wires->rate_bits);
     unsigned stride = 1;
-    P2_TRY(gates_validate(ctx, gates, wires, constants_sigmas, sigmas_first_col, "gate_sums", &stride));
+    P2_TRY(gates_validate(ctx, gates, wires, constants_sigmas, sigmas_first_col, quotient_degree_factor, "gate_sums", &stride));
     const unsigned log_nq = wires->log_n + qbits;
     const size_t m = (size_t)1 << log_nq;
     PoolBuf d_out(ctx), d_apow(ctx);
@@ -1550,7 +1554,7 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
             P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: the lookup selectors do not fit the constants_sigmas commitment");
     }
     unsigned gs_stride = 0;
-    if (with_gates) P2_TRY(gates_validate(ctx, gs, wires, constants_sigmas, sigmas_first_col, "quotient_polys_gates", &gs_stride));
+    if (with_gates) P2_TRY(gates_validate(ctx, gs, wires, constants_sigmas, sigmas_first_col, quotient_degree_factor, "quotient_polys_gates", &gs_stride));
     const size_t n_apow = lk ? (size_t)num_challenges * ((size_t)num_challenges * lk_Kc + 1) : 0, n_evals = lk ? (size_t)num_challenges * lk->num_luts : 0;
     const size_t n_gpow = (size_t)num_challenges * gs_stride;
     PoolBuf d_work(ctx), d_small(ctx), d_gate(ctx);

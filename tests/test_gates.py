@@ -91,26 +91,26 @@ def _instance(seed, gates, num_selectors, log_n, nls=0, satisfied=False, nc=4, q
     return q
 
 
-def _ldes(q, names=("wires", "cs")):
-    return {name: vr.Lde(vr.interpolate_columns(q[name]), q["log_n"], RATE_BITS) for name in names}
+def _ldes(q, names=("wires", "cs"), rate_bits=RATE_BITS):
+    return {name: vr.Lde(vr.interpolate_columns(q[name]), q["log_n"], rate_bits) for name in names}
 
 
 def _ref_sums(q, ldes, gates=None, alphas=None):
-    """the restatement at every point of the quotient coset: [len(alphas)][n << qbits]"""
+    """the restatement at every point of the quotient coset: [len(alphas)][n << qbits]; the rate is the LDEs' own"""
     qbits = vr.log2_ceil(q["qdf"])
     m = q["n"] << qbits
     alphas = q["alphas"] if alphas is None else alphas
     out = np.zeros((len(alphas), m), dtype=np.uint64)
     for i in range(m):
-        (li, step), _ = vr.quotient_rows(i, q["log_n"], RATE_BITS, qbits)
+        (li, step), _ = vr.quotient_rows(i, q["log_n"], ldes["wires"].rate_bits, qbits)
         out[:, i] = gr.reduced_sums(vr.BASE, q["gates"] if gates is None else gates, q["ns"], q["nls"], vr.get_lde_values(ldes["wires"], li, step),
                                     vr.get_lde_values(ldes["cs"], li, step), q["pih"], alphas)
     return out
 
 
-def _commit(eng, q, names=("wires", "cs")):
+def _commit(eng, q, names=("wires", "cs"), rate_bits=RATE_BITS, hasher=None):
     from plonky2_amd.fri.oracle import PolynomialBatch
-    return {name: PolynomialBatch.from_values(q[name], RATE_BITS, False, 0, engine=eng) for name in names}
+    return {name: PolynomialBatch.from_values(q[name], rate_bits, False, 0, engine=eng, hasher=hasher) for name in names}
 
 
 def _gate_set(q, gates=None, pih=None):
@@ -118,9 +118,9 @@ def _gate_set(q, gates=None, pih=None):
     return GateSet([g.descriptor() for g in (q["gates"] if gates is None else gates)], q["ns"], q["nls"], pih or q["pih"])
 
 
-def _device_sums(eng, q, b, nc, gates=None, pih=None):
+def _device_sums(eng, q, b, nc, gates=None, pih=None, alphas=None):
     from plonky2_amd.plonk.prover import gate_sums
-    return gate_sums(b["wires"], b["cs"], q["sigmas_first"], _gate_set(q, gates, pih), q["qdf"], q["alphas"][:nc], engine=eng)
+    return gate_sums(b["wires"], b["cs"], q["sigmas_first"], _gate_set(q, gates, pih), q["qdf"], (alphas or q["alphas"])[:nc], engine=eng)
 
 
 # ------------------------------------------------------------------ the restatement on its own
@@ -210,7 +210,7 @@ def _full(satisfied, qdf=QDF, log_n=6):
     return _FULL[key]
 
 
-@pytest.mark.parametrize("nc", [1, 2, 4])
+@pytest.mark.parametrize("nc", [1, 2, 3, 4])
 def test_gate_sums_of_the_full_set(eng, nc):
     """all eight kinds in three selector groups (the UNUSED_SELECTOR factor; rows whose selector is 0xFFFFFFFF in two groups),
     512 points"""
@@ -366,13 +366,13 @@ def test_errors_come_before_any_work(eng):
     nc, sf = 2, q["sigmas_first"]
     out = np.zeros((nc, 16 << 3), dtype=np.uint64)
 
-    def sums(gs, wires=None, cs=None, sigmas_first=sf):
-        return eng.lib.p2hot_gate_sums(eng.ctx, (wires or b["wires"])._h, (cs or b["cs"])._h, sigmas_first, gs.ptr if gs else None, 7,
+    def sums(gs, wires=None, cs=None, sigmas_first=sf, qdf=7):
+        return eng.lib.p2hot_gate_sums(eng.ctx, (wires or b["wires"])._h, (cs or b["cs"])._h, sigmas_first, gs.ptr if gs else None, qdf,
                                        _u64(q["alphas"]), nc, out.ctypes.data_as(C.c_void_p))
 
-    def quot(gs, wires=None):
+    def quot(gs, wires=None, qdf=7):
         h = C.c_void_p(1)
-        rc = eng.lib.p2hot_quotient_polys_gates(eng.ctx, (wires or b["wires"])._h, b["cs"]._h, sf, b["zs"]._h, _u64(q["k_is"]), NUM_ROUTED, 7,
+        rc = eng.lib.p2hot_quotient_polys_gates(eng.ctx, (wires or b["wires"])._h, b["cs"]._h, sf, b["zs"]._h, _u64(q["k_is"]), NUM_ROUTED, qdf,
                                                 _u64(q["betas"]), _u64(q["gammas"]), _u64(q["alphas"]), nc, None, gs.ptr if gs else None, None,
                                                 C.byref(h))
         assert rc == _lib.OK or not h.value          # chunks_out is null after every failure
@@ -398,6 +398,17 @@ def test_errors_come_before_any_work(eng):
     for gs, code in cases:
         assert sums(gs) == code and quot(gs) == code, gs.gates
         assert eng.lib.p2hot_last_error(eng.ctx)
+    # a BaseSum base above the quotient degree factor: its range constraint has degree B, and the kernel's loop is B - 1 long.
+    # (factor + 1 and no larger base: before the bound a large one WAS the long-running kernel)
+    # (accepted at factor 8 only: there the trim drops nothing, and this instance does not satisfy a BaseSum row)
+    for base, qdf, code in ((9, 8, _lib.EINVAL), (8, 7, _lib.EINVAL), (8, 8, _lib.OK)):
+        gs = one(gr.BASE_SUM, p0=4, p1=base)
+        assert sums(gs, qdf=qdf) == code and quot(gs, qdf=qdf) == code, (base, qdf)
+        if code != _lib.OK:
+            msg = eng.lib.p2hot_last_error(eng.ctx)
+            assert b"BaseSum base %d" % base in msg and b"factor %d" % qdf in msg, msg
+    assert eng.lib.p2hot_ctx_trim(eng.ctx) == 0
+    _base_sum_bound_of_the_lookup_variant(eng)
     narrow = PolynomialBatch.from_values(q["wires"][:134], RATE_BITS, False, 0, engine=eng)
     assert sums(one(gr.POSEIDON), wires=narrow) == _lib.EINVAL and sums(one(gr.POSEIDON)) == _lib.OK
     null_gates = GateSet([], 3)
@@ -411,6 +422,37 @@ def test_errors_come_before_any_work(eng):
     for other in (small, rate2):
         assert sums(good, wires=other) == _lib.EINVAL and quot(good, wires=other) == _lib.EINVAL
     assert sums(good) == _lib.OK and quot(good) == _lib.OK and out.any()
+
+
+def _base_sum_bound_of_the_lookup_variant(eng):
+    """p2hot_quotient_polys_lookup_gates on the lookup instance of test_lookup_quotient_equals_the_host_gate_sums_path (factor 4):
+    base 5 is refused before anything is enqueued, base 4 runs"""
+    from plonky2_amd import _lib
+    from tests import test_lookup as tl
+    nc, num_routed, qdf = 2, 12, 4
+    q = tl._instance(np.random.default_rng(22), nc, qdf, num_routed, 3, 4, satisfied=False)
+    nls = 4 + len(q["luts"])
+    b = tl._commit(eng, q)
+    vals = np.zeros((nc, 16 << 2), dtype=np.uint64)
+    from plonky2_amd.plonk.prover import GateSet
+    for base, code in ((5, _lib.EINVAL), (4, _lib.OK)):
+        gs = GateSet([(gr.BASE_SUM, 0, 0, 0, 1, 6, base)], 2, nls)
+        vals[:] = 0
+        rc = eng.lib.p2hot_quotient_polys_lookup_gates(
+            eng.ctx, b["wires"]._h, b["cs"]._h, q["sigmas_first"], b["zs"]._h, _u64(q["k_is"]), num_routed, qdf, _u64(q["betas"]), _u64(q["gammas"]),
+            _u64(q["alphas"]), nc, None, q["lu_slots"], q["lut_slots"], len(q["luts"]), tl.SEL_FIRST, _u64(q["deltas"]), _u64(q["evals"]), gs.ptr,
+            vals.ctypes.data_as(C.c_void_p), None)
+        msg = eng.lib.p2hot_last_error(eng.ctx)
+        assert rc == code, (base, msg)
+        assert vals.any() if code == _lib.OK else not vals.any() and b"BaseSum base 5" in msg and b"factor 4" in msg, msg
+    assert eng.lib.p2hot_ctx_trim(eng.ctx) == 0
+
+
+def test_base_sum_base_equal_to_the_factor(eng):
+    """the largest base the bound admits: BaseSum<8> alone in its group at factor 8 (group size 1 + degree 8 = factor + 1)"""
+    q = _instance(61, _alone(gr.BASE_SUM, 5, 8), 1, 4, nc=2)
+    exp = _ref_sums(q, _ldes(q))
+    assert (_device_sums(eng, q, _commit(eng, q), 2) == exp).all() and exp.all()
 
 
 def test_errors_commitment_of_another_context(emu):

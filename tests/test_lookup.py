@@ -10,7 +10,7 @@ import pytest
 
 from tests import lookup_ref as lr
 from tests import vanishing_ref as vr
-from tests.conftest import P
+from tests.conftest import P, rand_field
 from tests.pyref import G
 
 NUM_CONSTANTS = 2            # constants_sigmas: [c0, c1, the 4 + num_luts lookup selectors, sigma_0 ...]
@@ -164,19 +164,74 @@ def test_lookup_polys_vs_restatement(eng, num_routed, lookup_degree, log_n, nc, 
     assert b.merkle_tree.cap.entries.any() and (b.merkle_tree.cap.entries == ref.merkle_tree.cap.entries).all()
 
 
+def _carries_per(region):
+    """chunks per thread of lookup::lookup_carries_kernel for one region: SCAN_CHUNK = 4 rows per chunk (csrc/lookup.hpp), one block
+    of 1024 threads over the chunks (its launch in p2hot_lookup_polys, csrc/host_prover.hpp)"""
+    last_lu, _, first_lut = region
+    n_chunks = lr.div_ceil(first_lut - last_lu + 1, 4)
+    return n_chunks, lr.div_ceil(n_chunks, 1024)
+
+
 def test_lookup_polys_scan_boundaries(eng):
     """a LUT region of 300 rows under an LU region of 3000 rows: both span several workgroups of the scan kernels and (the LU one)
-    of the row kernel, and the carries cross from one to the other.  Random wires: the values are defined for any witness"""
+    of the row kernel, and the carries cross from one to the other.  Random wires: the values are defined for any witness.
+
+    Second case, 2^13 rows: a region of 8002 rows = 2001 chunks, so every thread of the carries kernel reduces and replays TWO
+    chunks, thread 1000 one (its `hi` is clamped) and threads 1001.. none (`lo` clamped).  Its 1102 LookupTable rows end inside
+    chunk 275, the second chunk of thread 137's pair.  It is processed after an adjacent region made of LookupTable rows only, whose
+    last row is this one's first_lut + 1: both seeds (RE and the last SLDC) are nonzero."""
     rng = np.random.default_rng(12)
     num_routed, lookup_degree, log_n = 12, 3, 12
     wires = _rand(rng, num_routed, 1 << log_n)
     rows = [(500, 3500, 3799)]
+    assert _carries_per(rows[0])[1] == 1
     for nc in (1, 2):
         deltas = _deltas(rng, nc)
         exp = np.asarray(lr.compute_all_lookup_polys(wires, deltas, rows, num_routed, lookup_degree + 1), dtype=np.uint64)
         _, host = _library_polys(eng, wires, rows, deltas, num_routed, lookup_degree)
         assert (host == exp).all()
         assert not host[:, :500].any() and not host[:, 3800:].any() and host[1:3, 500].all() and not host[0, :3500].any()
+    log_n = 13
+    wires = _rand(rng, num_routed, 1 << log_n)
+    big, above = (101, 7001, 8102), (8103, 8103, 8150)
+    n_chunks, per = _carries_per(big)
+    len_lut = big[2] - big[1] + 1
+    assert per == 2 and 1024 < n_chunks <= 2048 and n_chunks % 2 == 1 and len_lut % 4 and len_lut % 8
+    assert (len_lut // 4) % 2 == 1          # the chunk that holds the LookupTable / Lookup boundary is the second of a thread's two
+    assert above[0] == big[2] + 1 and _carries_per(above)[1] == 1
+    rows = [above, big]
+    for nc in (1, 2):
+        deltas = _deltas(rng, nc)
+        exp = np.asarray(lr.compute_all_lookup_polys(wires, deltas, rows, num_routed, lookup_degree + 1), dtype=np.uint64)
+        _, host = _library_polys(eng, wires, rows, deltas, num_routed, lookup_degree)
+        S = lr.div_ceil(lr.num_lu_slots(num_routed), lookup_degree)
+        assert exp[::S + 1, big[2] + 1].all() and exp[S::S + 1, big[2] + 1].all()      # the seeds: RE and the last SLDC of every challenge
+        assert (host == exp).all()
+        assert not host[:, :big[0]].any() and not host[:, above[2] + 1:].any() and not host[::S + 1, big[0]:big[1]].any()
+
+
+def test_lookup_polys_noncanonical_host_words(eng):
+    """the caller's words are raw GoldilocksField(u64): wires in [P, 2^64) -- 2^64 - 1 and P among them -- give the polynomials of
+    the reduced words, canonical; deltas handed over as delta + P give the same bytes"""
+    rng = np.random.default_rng(77)
+    num_routed, lookup_degree, log_n, nc = 12, 3, 5, 2
+    rows = _regions(num_routed, _spec_for(num_routed, log_n, adjacent=True))
+    wires = rand_field(rng, num_routed, 1 << log_n, noncanonical=True)
+    (last_lu, last_lut, first_lut) = rows[0]
+    wires[1][last_lu] = (1 << 64) - 1          # a looking output, a looked input
+    wires[3][first_lut] = P
+    assert (wires >= P).sum() > 2
+    reduced = np.asarray([[int(v) % P for v in col] for col in wires], dtype=object)
+    small = rng.integers(1, (1 << 32) - 1, size=4, dtype=np.uint64)
+    deltas = [[int(v) for v in small], [int(v) for v in _rand(rng, 4)]]
+    deltas[1][lr.DELTA] = int(small[0]) // 2 + 7
+    exp = np.asarray(lr.compute_all_lookup_polys(reduced, deltas, rows, num_routed, lookup_degree + 1), dtype=np.uint64)
+    cols, host = _library_polys(eng, wires, rows, deltas, num_routed, lookup_degree)
+    assert (host < P).all() and (host == exp).all() and (cols.host() == exp).all()
+    shifted = [[d + P if d + P < 1 << 64 else d for d in ds] for ds in deltas]
+    assert sum(a != b for da, db in zip(deltas, shifted) for a, b in zip(da, db)) == 5
+    cols2, host2 = _library_polys(eng, wires, rows, shifted, num_routed, lookup_degree)
+    assert host2.tobytes() == host.tobytes() and cols2.host().tobytes() == host.tobytes()
 
 
 def test_lookup_polys_follow_the_callers_region_order(eng):
@@ -270,6 +325,9 @@ def _library_quotient(eng, q, b, gate_sums):
 
 
 QUOTIENT_SHAPES = [(12, 4), (14, 3), (20, 3), (80, 8)]      # num_routed, quotient degree factor (lookup_degree + 1)
+# ... with the number of challenges: 1 and 2 everywhere, 3 (lookup_terms_kernel<3>, quotient_perm_kernel<3, 0>; the Zs batch of
+# _instance is as wide as its challenges ask) on the shape whose last LookupGate group has one slot
+QUOTIENT_CASES = [(r, f, nc) for nc in (1, 2) for r, f in QUOTIENT_SHAPES] + [(14, 3, 3)]
 _SHARED = {}
 
 
@@ -286,8 +344,7 @@ def _shared(num_routed, qdf, nc, satisfied):
 
 
 @pytest.mark.parametrize("satisfied", [True, False])
-@pytest.mark.parametrize("nc", [1, 2])
-@pytest.mark.parametrize("num_routed,qdf", QUOTIENT_SHAPES)
+@pytest.mark.parametrize("num_routed,qdf,nc", QUOTIENT_CASES)
 def test_quotient_values_vs_restatement(eng, num_routed, qdf, nc, satisfied):
     """every point of the quotient coset (rate_bits 3, 2^4 rows), with and without gate_sums, on a satisfied and on a random instance"""
     q, ldes, gs, exp = _shared(num_routed, qdf, nc, satisfied)
