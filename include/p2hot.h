@@ -569,7 +569,7 @@ int p2hot_quotient_polys_lookup(p2hot_ctx *ctx, const p2hot_batch *wires, const 
 int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2hot_cols *b, p2hot_cols **out);
 
 /* ---------------------------------------------------------------- the standard gates' constraints (D = 2)
- * evaluate_gate_constraints_base_batch (plonk/vanishing_poly.rs:702-728) on the quotient coset for eight gates of the reference.
+ * evaluate_gate_constraints_base_batch (plonk/vanishing_poly.rs:702-728) on the quotient coset for fourteen gates of the reference.
  * A gate of common_data.gates is described by
  *   kind            P2HOT_GATE_*
  *   row             its index in common_data.gates: the `row` compute_filter excludes (gates/gate.rs:326-333)
@@ -597,9 +597,37 @@ int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2hot_cols *b, 
  *                   S-box inputs of full rounds 1..3, of the 22 partial rounds in their FAST form (hash/poseidon.rs:365-373,
  *                   :415-441, :516-542), of the second four full rounds, and the 12 outputs; the state continues from the wire
  *                   after every constrained S-box input
- * Every other gate of the reference stays the caller's (the host gate_sums of the entry points below). */
+ * The six gates a recursive verifier circuit adds under standard_recursion_config (the second enum below, kinds 16..21; an
+ * "extension element on wires c, c + 1" is c + (c + 1) X in F[X]/(X^2 - 7), and a constraint on one yields component 0, then 1):
+ *   POSEIDON_MDS    out_k - MDS(inputs)_k, k < 12; input k on wires 2k, 2k + 1, output k on 24 + 2k, 24 + 2k + 1: 48 wires, 24
+ *                   constraints                                                                         (poseidon_mds.rs:156-175)
+ *   REDUCING        param0 = num_coeffs >= 1.  output on wires 0..2, alpha 2..4, old_acc 4..6, base-field coeffs 6 .. 6 + nc,
+ *                   acc_k on 6 + nc + 2k for k < nc - 1, the last accumulator is the output; constraint pair k =
+ *                   acc alpha + coeff_k - acc_k, then acc continues from the WIRE acc_k: 3 nc + 4 wires   (reducing.rs:107-127)
+ *   REDUCING_EXT    the same with extension coeffs on 6 + 2k and the accumulators from 6 + 2 nc: 4 nc + 4 wires
+ *                                                                                                       (reducing_extension.rs:109-128)
+ *   RANDOM_ACCESS   param0 = num_copies >= 1, param1 = bits | num_extra_constants << 8, 1 <= bits <= 6, bits + 1 <=
+ *                   quotient_degree_factor.  Copy c: access_index on wire s c, claimed element s c + 1, the 2^bits list items from
+ *                   s c + 2 (s = 2 + 2^bits); its bits on s copies + extra + c bits + l.  Per copy b (b - 1) per bit, the bits
+ *                   folded big endian (acc + acc + b) minus access_index, the list folded pairwise x + b (y - x), bit 0 first,
+ *                   minus claimed; then constants[k] - wires[s copies + k], k < extra                    (random_access.rs:302-343)
+ *   EXPONENTIATION  param0 = num_power_bits >= 1, quotient_degree_factor >= 4.  base on wire 0, little-endian power bits 1 .. 1 + n,
+ *                   output 1 + n, intermediates from 2 + n; constraint k = prev (bit base + 1 - bit) - inter_k with prev = 1 or
+ *                   inter_{k-1}^2 and bit = power_bits[n - 1 - k]; last output - inter_{n-1}             (exponentiation.rs:210-243)
+ *   COSET_INTERPOLATION  param0 = subgroup_bits 1..5 (N = 2^subgroup_bits points), param1 = degree d, 2 <= d <= N, d <=
+ *                   quotient_degree_factor; ni = (N - 2) / (d - 1).  shift on wire 0, value k on 1 + 2k, evaluation point 1 + 2N,
+ *                   evaluation value next, from 1 + 2N + 4 the ni intermediate evals, the ni intermediate prods, the shifted point.
+ *                   point - shifted shift; the barycentric walk eval <- eval (x - x_k) + (w_k v_k) prod, prod <- prod (x - x_k)
+ *                   from (0, 1) over the first d points of two_adic_subgroup(subgroup_bits); per intermediate inter_eval - eval,
+ *                   inter_prod - prod, and the walk goes on from the WIRES over the next d - 1 points (clipped at N); last
+ *                   evaluation_value - eval.  The library computes the domain and the weights w_k = x_k / N itself
+ *                                                                                                       (coset_interpolation.rs:251-298, :553-580)
+ * Every other gate of the reference that has constraints of its own stays the caller's (the host gate_sums of the entry points
+ * below): LookupGate / LookupTableGate have none, so only user-defined gates do.  Kinds 8..15 and above 21 are P2HOT_EUNSUPPORTED. */
 enum { P2HOT_GATE_NOOP, P2HOT_GATE_CONSTANT, P2HOT_GATE_PUBLIC_INPUT, P2HOT_GATE_ARITHMETIC,
        P2HOT_GATE_ARITHMETIC_EXT, P2HOT_GATE_MUL_EXT, P2HOT_GATE_BASE_SUM, P2HOT_GATE_POSEIDON };
+enum { P2HOT_GATE_POSEIDON_MDS = 16, P2HOT_GATE_REDUCING, P2HOT_GATE_REDUCING_EXT, P2HOT_GATE_RANDOM_ACCESS,
+       P2HOT_GATE_EXPONENTIATION, P2HOT_GATE_COSET_INTERPOLATION };
 typedef struct p2hot_gate { uint32_t kind, row, selector_index, group_first, group_end, param0, param1; } p2hot_gate;
 typedef struct p2hot_gate_set { const p2hot_gate *gates; uint32_t num_gates, num_selectors, num_lookup_selectors;
                                 uint64_t public_inputs_hash[4]; } p2hot_gate_set;
@@ -607,7 +635,8 @@ typedef struct p2hot_gate_set { const p2hot_gate *gates; uint32_t num_gates, num
  * wires / constants_sigmas as in p2hot_quotient_polys (any hasher); sigmas_first_col bounds the constants a gate may read.
  * Raised before anything is enqueued -- P2HOT_EUNSUPPORTED: an unknown kind.  P2HOT_EINVAL: row outside its group (or a group of
  * more than 256 gates), selector_index >= num_selectors, selectors + lookup selectors + the constants a gate reads beyond
- * sigmas_first_col, a gate's wires beyond the wires commitment, B < 2, B > quotient_degree_factor or num_limbs > 63, gates->gates null with num_gates > 0, a
+ * sigmas_first_col, a gate's wires beyond the wires commitment, B < 2, B > quotient_degree_factor or num_limbs > 63, a parameter of
+ * the kinds 16..21 outside the range stated above or a degree above quotient_degree_factor, gates->gates null with num_gates > 0, a
  * null set, commitments of another context, degree or rate, num_challenges outside 1..4. */
 int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
                     const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,

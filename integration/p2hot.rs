@@ -175,6 +175,13 @@ pub const P2HOT_GATE_ARITHMETIC_EXT: u32 = 4;
 pub const P2HOT_GATE_MUL_EXT: u32 = 5;
 pub const P2HOT_GATE_BASE_SUM: u32 = 6;
 pub const P2HOT_GATE_POSEIDON: u32 = 7;
+/// the gates a recursive verifier circuit adds (the header's second enum)
+pub const P2HOT_GATE_POSEIDON_MDS: u32 = 16;
+pub const P2HOT_GATE_REDUCING: u32 = 17;
+pub const P2HOT_GATE_REDUCING_EXT: u32 = 18;
+pub const P2HOT_GATE_RANDOM_ACCESS: u32 = 19;
+pub const P2HOT_GATE_EXPONENTIATION: u32 = 20;
+pub const P2HOT_GATE_COSET_INTERPOLATION: u32 = 21;
 
 /// p2hot_gate: one entry of common_data.gates (its index, its selector group, its parameters)
 #[repr(C)]
@@ -1312,10 +1319,49 @@ pub fn eval_commitment<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>,
 // ------------------------------------------------------------------------------------------------
 // compute_quotient_polys (plonk/prover.rs:609-815): the permutation argument's share on the GPU
 // ------------------------------------------------------------------------------------------------
+/// The field `name: <integer>` of a gate's Debug form (`id()`), e.g. `bits` of "RandomAccessGate { bits: 4, num_copies: 4, .. }".
+/// The name must start the field: "bits" does not match inside "subgroup_bits".
+fn debug_field(id: &str, name: &str) -> Option<usize> {
+    let key = format!("{name}: ");
+    let mut from = 0;
+    while let Some(at) = id[from..].find(&key) {
+        let at = from + at;
+        let starts_field = id[..at].chars().next_back().map_or(true, |c| !(c.is_alphanumeric() || c == '_'));
+        if starts_field {
+            let digits: String = id[at + key.len()..].chars().take_while(|c| c.is_ascii_digit()).collect();
+            return digits.parse().ok();
+        }
+        from = at + key.len();
+    }
+    None
+}
+
+/// (wires, constraints) of a descriptor of the recursion kinds: the table of include/p2hot.h (gates::shape)
+fn recursion_gate_shape(kind: u32, param0: usize, param1: usize) -> Option<(usize, usize)> {
+    Some(match kind {
+        P2HOT_GATE_POSEIDON_MDS => (48, 24),
+        P2HOT_GATE_REDUCING => (3 * param0 + 4, 2 * param0),
+        P2HOT_GATE_REDUCING_EXT => (4 * param0 + 4, 2 * param0),
+        P2HOT_GATE_RANDOM_ACCESS => {
+            let (bits, extra) = (param1 & 0xFF, param1 >> 8);
+            ((2 + (1 << bits) + bits) * param0 + extra, param0 * (bits + 2) + extra)
+        }
+        P2HOT_GATE_EXPONENTIATION => (2 + 2 * param0, param0 + 1),
+        P2HOT_GATE_COSET_INTERPOLATION => {
+            let n = 1usize << param0;
+            let ni = (n - 2) / (param1 - 1);
+            (1 + 2 * n + 4 + 2 * (2 * ni + 1), 4 + 4 * ni)
+        }
+        _ => return None,
+    })
+}
+
 /// The descriptor of a gate the library evaluates on the device (include/p2hot.h: Noop, Constant, PublicInput, Arithmetic,
-/// ArithmeticExtension, MulExtension, BaseSum<B>, Poseidon; D = 2), or `None` for every other gate.  The kind is read from the prefix
+/// ArithmeticExtension, MulExtension, BaseSum<B>, Poseidon, and the recursion gates PoseidonMds, Reducing, ReducingExtension,
+/// RandomAccess, Exponentiation, CosetInterpolation; D = 2), or `None` for every other gate.  The kind is read from the prefix
 /// of `id()` (the Debug form of the gate struct), the parameters from `num_constraints()` / `num_wires()`, BaseSum's base from the
-/// id's suffix (gates/base_sum.rs:55-57: "... + Base: B").
+/// id's suffix (gates/base_sum.rs:55-57: "... + Base: B"), RandomAccess' and CosetInterpolation's parameters from the Debug form's
+/// fields.  A recursion descriptor whose shape disagrees with the gate's own `num_wires()` / `num_constraints()` stays unmapped.
 fn gate_descriptor<F: RichField + Extendable<D>, const D: usize>(
     id: &str,
     num_constraints: usize,
@@ -1348,9 +1394,37 @@ fn gate_descriptor<F: RichField + Extendable<D>, const D: usize>(
         (P2HOT_GATE_BASE_SUM, num_wires - 1, base)
     } else if id.starts_with("PoseidonGate(") && num_constraints == 123 && num_wires == 135 {
         (P2HOT_GATE_POSEIDON, 0, 0)
+    } else if id.starts_with("PoseidonMdsGate(") {
+        (P2HOT_GATE_POSEIDON_MDS, 0, 0)
+    } else if id.starts_with("ReducingGate {") {
+        (P2HOT_GATE_REDUCING, num_constraints / D, 0)
+    } else if id.starts_with("ReducingExtensionGate {") {
+        (P2HOT_GATE_REDUCING_EXT, num_constraints / D, 0)
+    } else if id.starts_with("ExponentiationGate {") {
+        (P2HOT_GATE_EXPONENTIATION, num_constraints.checked_sub(1)?, 0)
+    } else if id.starts_with("RandomAccessGate {") {
+        let (bits, extra) = (debug_field(id, "bits")?, debug_field(id, "num_extra_constants")?);
+        if !(1..=6).contains(&bits) || extra >= 1 << 16 {
+            return None;
+        }
+        (P2HOT_GATE_RANDOM_ACCESS, debug_field(id, "num_copies")?, bits | extra << 8)
+    } else if id.starts_with("CosetInterpolationGate {") {
+        let (subgroup_bits, degree) = (debug_field(id, "subgroup_bits")?, debug_field(id, "degree")?);
+        if !(1..=5).contains(&subgroup_bits) || degree < 2 || degree > 1 << subgroup_bits {
+            return None;
+        }
+        (P2HOT_GATE_COSET_INTERPOLATION, subgroup_bits, degree)
     } else {
         return None;
     };
+    if kind >= P2HOT_GATE_POSEIDON_MDS {
+        if param0 == 0 && kind != P2HOT_GATE_POSEIDON_MDS {
+            return None;
+        }
+        if recursion_gate_shape(kind, param0, param1)? != (num_wires, num_constraints) {
+            return None;
+        }
+    }
     Some(P2hotGate {
         kind,
         row: row as u32,
@@ -1363,7 +1437,7 @@ fn gate_descriptor<F: RichField + Extendable<D>, const D: usize>(
 }
 
 /// The vanishing polynomial's terms are `[L_0 (Z - 1) ..] ++ [partial product checks ..] ++ [gate constraint terms ..]`
-/// (plonk/vanishing_poly.rs:326-330) reduced with the powers of each alpha.  The gate terms of the eight standard gates
+/// (plonk/vanishing_poly.rs:326-330) reduced with the powers of each alpha.  The gate terms of the fourteen gates the library knows
 /// (`gate_descriptor`) are evaluated on the device by `p2hot_quotient_polys_gates` / `_lookup_gates`; every OTHER gate of the
 /// circuit is evaluated HERE by the reference's own `eval_filtered_base_batch` on the reference's own point batches
 /// (prover.rs:684-779, BATCH_SIZE = 32, added up as vanishing_poly.rs:702-728 does) and reduced into the residual `gate_sums` the

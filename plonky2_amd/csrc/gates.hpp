@@ -36,6 +36,20 @@ __host__ __device__ inline void shape(const p2hot_gate &g, unsigned &wires, unsi
         case P2HOT_GATE_MUL_EXT: wires = 6 * g.param0, consts = 1, constraints = 2 * g.param0; break;
         case P2HOT_GATE_BASE_SUM: wires = constraints = 1 + g.param0; break;
         case P2HOT_GATE_POSEIDON: wires = POSEIDON_WIRES, constraints = POSEIDON_CONSTRAINTS; break;
+        case P2HOT_GATE_POSEIDON_MDS: wires = 48, constraints = 24; break;
+        case P2HOT_GATE_REDUCING: wires = 3 * g.param0 + 4, constraints = 2 * g.param0; break;
+        case P2HOT_GATE_REDUCING_EXT: wires = 4 * g.param0 + 4, constraints = 2 * g.param0; break;
+        case P2HOT_GATE_RANDOM_ACCESS: {  // param1 = bits | num_extra_constants << 8
+            const unsigned bits = g.param1 & 0xFFu, extra = g.param1 >> 8;
+            wires = (2 + (bits < 32 ? 1u << bits : 0u) + bits) * g.param0 + extra, consts = extra, constraints = g.param0 * (bits + 2) + extra;
+            break;
+        }
+        case P2HOT_GATE_EXPONENTIATION: wires = 2 + 2 * g.param0, constraints = g.param0 + 1; break;
+        case P2HOT_GATE_COSET_INTERPOLATION: {  // param0 = subgroup_bits, param1 = degree
+            const unsigned n = g.param0 < 32 ? 1u << g.param0 : 0u, ni = g.param1 > 1 && n >= 2 ? (n - 2) / (g.param1 - 1) : 0;
+            wires = 1 + 2 * n + 4 + 2 * (2 * ni + 1), constraints = 4 + 4 * ni;
+            break;
+        }
         default: break;
     }
 }

@@ -1385,7 +1385,8 @@ static int gates_validate(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_
     if (sigmas_first_col > constants_sigmas->W) P2_FAIL(ctx, P2HOT_EINVAL, "%s: sigmas_first_col beyond the constants_sigmas commitment", what);
     for (unsigned k = 0; k < gs->num_gates; ++k) {
         const p2hot_gate &g = gs->gates[k];
-        if (g.kind > P2HOT_GATE_POSEIDON) P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: gate %u has the unknown kind %u", what, k, g.kind);
+        if (g.kind > P2HOT_GATE_POSEIDON && (g.kind < P2HOT_GATE_POSEIDON_MDS || g.kind > P2HOT_GATE_COSET_INTERPOLATION))
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: gate %u has the unknown kind %u", what, k, g.kind);
         if (g.row < g.group_first || g.row >= g.group_end) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: row %u outside its group [%u, %u)", what, k, g.row, g.group_first, g.group_end);
         if (g.group_end - g.group_first > 256) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: a selector group of %u gates (at most 256)", what, k, g.group_end - g.group_first);
         if (g.selector_index >= gs->num_selectors) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: selector %u of %u", what, k, g.selector_index, gs->num_selectors);
@@ -1395,6 +1396,40 @@ static int gates_validate(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_
         if (g.kind == P2HOT_GATE_BASE_SUM && g.param1 > quotient_degree_factor)
             P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: BaseSum base %u above the quotient degree factor %u", what, k, g.param1, quotient_degree_factor);
         if (g.param0 > (1u << 24)) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: parameter %u", what, k, g.param0);
+        // the recursion kinds (gates_recursion.hpp): parameter ranges, then the degree against the factor for the reason BaseSum's base
+        // is bounded -- a circuit whose factor is below the gate's degree cannot hold it, and the bounds keep the kernel's loops short
+        const unsigned qdf = quotient_degree_factor;
+        switch (g.kind) {
+            case P2HOT_GATE_REDUCING:
+            case P2HOT_GATE_REDUCING_EXT: {
+                const char *name = g.kind == P2HOT_GATE_REDUCING ? "Reducing" : "ReducingExtension";
+                if (g.param0 == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: %s with 0 coefficients", what, k, name);
+                if (qdf < 2) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: %s degree 2 above the quotient degree factor %u", what, k, name, qdf);
+                break;
+            }
+            case P2HOT_GATE_EXPONENTIATION:
+                if (g.param0 == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: Exponentiation with 0 power bits", what, k);
+                if (qdf < 4) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: Exponentiation degree 4 above the quotient degree factor %u", what, k, qdf);
+                break;
+            case P2HOT_GATE_RANDOM_ACCESS: {
+                const unsigned bits = gates::ra_bits(g), extra = gates::ra_extra(g);
+                if (g.param0 == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: RandomAccess with 0 copies", what, k);
+                if (bits < 1 || bits > gates::MAX_ACCESS_BITS) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: RandomAccess bits %u (1..%u)", what, k, bits, gates::MAX_ACCESS_BITS);
+                if (extra > (1u << 16)) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: RandomAccess with %u extra constants", what, k, extra);
+                if (bits + 1 > qdf)
+                    P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: RandomAccess bits %u: degree %u above the quotient degree factor %u", what, k, bits, bits + 1, qdf);
+                break;
+            }
+            case P2HOT_GATE_COSET_INTERPOLATION:
+                if (g.param0 < 1 || g.param0 > gates::MAX_SUBGROUP_BITS)
+                    P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: CosetInterpolation subgroup_bits %u (1..%u)", what, k, g.param0, gates::MAX_SUBGROUP_BITS);
+                if (g.param1 < 2 || g.param1 > (1u << g.param0))
+                    P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: CosetInterpolation degree %u over %u points (2..%u)", what, k, g.param1, 1u << g.param0, 1u << g.param0);
+                if (g.param1 > qdf)
+                    P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u: CosetInterpolation degree %u above the quotient degree factor %u", what, k, g.param1, qdf);
+                break;
+            default: break;
+        }
         unsigned nw, nk, ncons;
         gates::shape(g, nw, nk, ncons);
         if (nw > wires->W) P2_FAIL(ctx, P2HOT_EINVAL, "%s: gate %u reads %u wires of %zu", what, k, nw, wires->W);
@@ -1414,7 +1449,8 @@ static void gates_alpha_powers(u64 *apow, const uint64_t *alphas, unsigned nc, u
     }
 }
 
-// the launches: the cheap kinds MAX_CHEAP descriptors at a time, then one launch per PoseidonGate; all add into d_out [nc][1 << log_nq]
+// the launches: the cheap kinds MAX_CHEAP descriptors at a time, the recursion kinds the same way, then one launch per PoseidonMdsGate
+// and per PoseidonGate; all add into d_out [nc][1 << log_nq]
 static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
                         const u64 *d_apow, unsigned apow_stride, u64 *d_out, unsigned log_nq, unsigned nc) {
     const size_t m = (size_t)1 << log_nq;
@@ -1440,11 +1476,56 @@ static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_ba
     };
     for (unsigned k = 0; k < gs->num_gates; ++k) {
         const p2hot_gate &g = gs->gates[k];
-        if (g.kind == P2HOT_GATE_NOOP || g.kind == P2HOT_GATE_POSEIDON) continue;
+        if (g.kind == P2HOT_GATE_NOOP || g.kind >= P2HOT_GATE_POSEIDON) continue;  // (the recursion kinds have launches of their own below)
         a.gates[a.num_gates++] = g;
         if (a.num_gates == gates::MAX_CHEAP) P2_TRY(flush());
     }
     P2_TRY(flush());
+    // the recursion kinds: the descriptor loop of gates_recursion.hpp, the same Args plus CosetInterpolation's domain and 1 / N
+    {
+        gates::RecursionArgs ra{};
+        static_cast<gates::Args &>(ra) = a;
+        ra.num_gates = 0;
+        const u64 w32 = gl::root_of_unity(gates::MAX_SUBGROUP_BITS);
+        u64 x = 1;
+        for (unsigned t = 0; t < (1u << gates::MAX_SUBGROUP_BITS); ++t, x = gl::mul(x, w32)) ra.dom[t] = gl::canon(x);
+        for (unsigned b = 0; b <= gates::MAX_SUBGROUP_BITS; ++b) ra.ninv[b] = gl::canon(gl::inv((u64)1 << b));
+        auto flush_rec = [&]() -> int {
+            if (!ra.num_gates) return P2HOT_OK;
+            ProfScope prof(ctx, "gates_recursion");
+            switch (nc) {
+                case 1: P2HOT_LAUNCH((gates::recursion_gates_kernel<1>), grid, block, 0, ctx->stream, ra); break;
+                case 2: P2HOT_LAUNCH((gates::recursion_gates_kernel<2>), grid, block, 0, ctx->stream, ra); break;
+                case 3: P2HOT_LAUNCH((gates::recursion_gates_kernel<3>), grid, block, 0, ctx->stream, ra); break;
+                default: P2HOT_LAUNCH((gates::recursion_gates_kernel<4>), grid, block, 0, ctx->stream, ra); break;
+            }
+            P2_LAUNCH_CHECK(ctx);
+            ra.num_gates = 0;
+            return P2HOT_OK;
+        };
+        for (unsigned k = 0; k < gs->num_gates; ++k) {
+            const p2hot_gate &g = gs->gates[k];
+            if (g.kind < P2HOT_GATE_REDUCING || g.kind > P2HOT_GATE_COSET_INTERPOLATION) continue;
+            ra.gates[ra.num_gates++] = g;
+            if (ra.num_gates == gates::MAX_CHEAP) P2_TRY(flush_rec());
+        }
+        P2_TRY(flush_rec());
+    }
+    for (unsigned k = 0; k < gs->num_gates; ++k) {
+        if (gs->gates[k].kind != P2HOT_GATE_POSEIDON_MDS) continue;
+        gates::PoseidonArgs pa{};
+        pa.wires = a.wires, pa.wires_stride = a.wires_stride, pa.consts = a.consts, pa.consts_stride = a.consts_stride;
+        pa.apow = d_apow, pa.apow_stride = apow_stride, pa.out = d_out, pa.log_nq = log_nq, pa.num_selectors = gs->num_selectors;
+        pa.gate = gs->gates[k];
+        ProfScope prof(ctx, "gates_poseidon_mds");
+        switch (nc) {
+            case 1: P2HOT_LAUNCH((gates::mds_gate_kernel<1>), grid, block, 0, ctx->stream, pa); break;
+            case 2: P2HOT_LAUNCH((gates::mds_gate_kernel<2>), grid, block, 0, ctx->stream, pa); break;
+            case 3: P2HOT_LAUNCH((gates::mds_gate_kernel<3>), grid, block, 0, ctx->stream, pa); break;
+            default: P2HOT_LAUNCH((gates::mds_gate_kernel<4>), grid, block, 0, ctx->stream, pa); break;
+        }
+        P2_LAUNCH_CHECK(ctx);
+    }
     for (unsigned k = 0; k < gs->num_gates; ++k) {
         if (gs->gates[k].kind != P2HOT_GATE_POSEIDON) continue;
         gates::PoseidonArgs pa{};

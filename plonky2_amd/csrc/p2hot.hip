@@ -1,5 +1,5 @@
 // p2hot.hip -- context, pass planning and the C ABI of libp2hot (see include/p2hot.h).
-// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / gates.hpp.
+// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / gates.hpp / gates_recursion.hpp.
 #include "../../include/p2hot.h"
 
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "plonk.hpp"
 #include "lookup.hpp"
 #include "gates.hpp"
+#include "gates_recursion.hpp"
 #include "merkle.hpp"
 #include "keccak.hpp"
 #include "ntt.hpp"

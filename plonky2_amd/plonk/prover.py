@@ -228,6 +228,8 @@ def compute_quotient_polys_lookup(wires_commitment, constants_sigmas_commitment,
 
 # ------------------------------------------------------------------ the standard gates' constraints
 GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_MUL_EXT, GATE_BASE_SUM, GATE_POSEIDON = range(8)
+# the gates a recursive verifier circuit adds (the header's second enum)
+GATE_POSEIDON_MDS, GATE_REDUCING, GATE_REDUCING_EXT, GATE_RANDOM_ACCESS, GATE_EXPONENTIATION, GATE_COSET_INTERPOLATION = range(16, 22)
 
 
 class _P2hotGate(C.Structure):
@@ -244,7 +246,9 @@ class GateSet:
 
     gates: (kind, row, selector_index, group_first, group_end, param0, param1) per gate -- row = the gate's index in
     common_data.gates, [group_first, group_end) = selectors_info.groups[selector_index], param0 = num_consts / num_ops /
-    num_limbs, param1 = BaseSum's base; num_selectors = selectors_info.num_selectors(); num_lookup_selectors = 4 + num_luts of
+    num_limbs, param1 = BaseSum's base.  The recursion kinds: Reducing / ReducingExtension param0 = num_coeffs; Exponentiation
+    param0 = num_power_bits; RandomAccess param0 = num_copies, param1 = bits | num_extra_constants << 8; CosetInterpolation
+    param0 = subgroup_bits, param1 = degree; PoseidonMds takes none.  num_selectors = selectors_info.num_selectors(); num_lookup_selectors = 4 + num_luts of
     a circuit with lookup tables, else 0; public_inputs_hash: four field elements."""
 
     def __init__(self, gates, num_selectors, num_lookup_selectors=0, public_inputs_hash=(0, 0, 0, 0)):
