@@ -280,7 +280,8 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * from the main thread, outside its rayon closures).  Serialised by the library (busy guard): p2hot_commit*, p2hot_cols_upload,
  * p2hot_batch_coeffs / _rows / _paths / _digests / _subgroup_values, p2hot_eval_openings, p2hot_prove_openings, p2hot_partial_products,
  * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_quotient_polys_lookup, p2hot_lookup_polys, p2hot_cols_concat, p2hot_gate_sums,
- * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_ctx_trim.  p2hot_batch_free / p2hot_cols_free may be called from any thread at any time (a
+ * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_ctx_trim, p2hot_batch_oracle_commit,
+ * p2hot_batch_oracle_coeffs / _rows / _paths / _digests, p2hot_batch_prove_openings.  p2hot_batch_free / p2hot_batch_oracle_free / p2hot_cols_free may be called from any thread at any time (a
  * Drop, a finaliser): the block cache has its own lock.  Everything else -- the *_dev building blocks, p2hot_fri_commit,
  * p2hot_fri_pow, p2hot_challenger_* -- enqueues on the context's stream without a guard: the CALLER serialises those with
  * each other and with the host-pointer calls of the same context (the Rust shim holds the context behind a Mutex). */
@@ -658,6 +659,88 @@ int p2hot_quotient_polys_lookup_gates(p2hot_ctx *ctx, const p2hot_batch *wires, 
                                       unsigned num_luts, size_t lookup_selectors_first_col, const uint64_t *deltas,
                                       const uint64_t *lut_re_poly_evals, const p2hot_gate_set *gates, uint64_t *values_out,
                                       p2hot_cols **chunks_out);
+
+/* ================================================================ batch FRI: polynomials of several degrees, one tree, one proof
+ * plonky2/src/batch_fri/{oracle,prover}.rs over hash/batch_merkle_tree.rs.  Poseidon configuration, one GPU, blinding = false: a
+ * Keccak challenger or Keccak hasher bits are P2HOT_EUNSUPPORTED ("batch FRI is Poseidon-only").
+ *
+ * The tree (BatchMerkleTree::new, hash/batch_merkle_tree.rs:35-130).  Group j is a matrix of 2^h_j rows, h_0 > h_1 > ... (at most 8
+ * groups here, more is P2HOT_EUNSUPPORTED).  Segment 0 is the Merkle forest of group 0 capped at the layer of 2^h_1 nodes; the leaf
+ * i of segment j > 0 is that layer's digest i followed by row i of group j (4 + W_j words, hash_or_noop), capped at h_{j+1}; the
+ * last segment is capped at cap_height <= h_last.  `digests` is the segments' digest arrays back to back, each in the MerkleTree
+ * layout (merkle_tree.rs:50-57) of its own (2^h_j leaves, cap) pair: p2hot_num_digests(h_0, cap_height) digests in all.
+ *   d_groups     HOST table of n_groups DEVICE pointers: group j column-major, element (row, c) at d_groups[j][c * strides[j] + row]
+ *   strides, widths, log_heights  HOST [n_groups]; strides[j] >= 2^log_heights[j]
+ *   d_digests    DEVICE [p2hot_num_digests(log_heights[0], cap_height)][4], d_cap DEVICE [2^cap_height][4] */
+int p2hot_batch_merkle_dev(p2hot_ctx *ctx, const uint64_t *const *d_groups, const size_t *strides, const size_t *widths,
+                           const unsigned *log_heights, size_t n_groups, unsigned cap_height, uint64_t *d_digests, uint64_t *d_cap);
+/* BatchMerkleTree::values (batch_merkle_tree.rs:155-164) flattened, for m DEVICE leaf indices of the tallest group: row
+ * idx >> (h_0 - h_j) of every group, d_out [m][sum_j W_j].  An index >= 2^h_0: see p2hot_gather_rows_dev. */
+int p2hot_batch_merkle_rows_dev(p2hot_ctx *ctx, const uint64_t *const *d_groups, const size_t *strides, const size_t *widths,
+                                const unsigned *log_heights, size_t n_groups, const uint64_t *d_idx, size_t m, uint64_t *d_out);
+/* BatchMerkleTree::open_batch (batch_merkle_tree.rs:133-153): the merkle_tree_prove paths of the segments, concatenated:
+ * d_out [m][log_heights[0] - cap_height][4].  An index >= 2^h_0: see p2hot_merkle_paths_dev. */
+int p2hot_batch_merkle_paths_dev(p2hot_ctx *ctx, const uint64_t *d_digests, const unsigned *log_heights, size_t n_groups,
+                                 unsigned cap_height, const uint64_t *d_idx, size_t m, uint64_t *d_out);
+/* batch_fri_committed_trees (batch_fri/prover.rs:88-147): the commit phase over n_instances final polynomials of strictly decreasing
+ * degree.  d_coeffs_planar: HOST table of DEVICE pointers, instance j as planes [2][2^log_n[j]] (the nonzero coefficients; the
+ * reference passes instance 0 as padded coefficients and every instance as LDE values on g * H).  After round r's fold the
+ * instance whose length equals the folded length joins: final_values = final_values * beta_r + values_j (:124-135) -- computed here
+ * on the coefficients, s_k = beta_r f_k + p_k (g / shift')^k with shift' the coset shift after the fold, which is what the
+ * reference's coset_fft, pointwise sum and coset_ifft on shift' * H yield.  Every instance must join after some round (the
+ * reference's assert, :138), else P2HOT_EINVAL.  The remaining arguments and outputs are p2hot_fri_commit_dev's (with log_n[0] for
+ * log_n); the Option arguments do not exist on this path. */
+int p2hot_batch_fri_commit_dev(p2hot_ctx *ctx, const uint64_t *const *d_coeffs_planar, const unsigned *log_n, size_t n_instances,
+                               unsigned rate_bits, unsigned cap_height, const unsigned *arity_bits, unsigned n_rounds,
+                               p2hot_challenger *challenger, uint64_t *d_leaves_out, uint64_t *digests_out, int digests_on_device,
+                               uint64_t *caps_out, uint64_t *betas_out, uint64_t *final_out);
+
+/* A device-resident BatchFriOracle (batch_fri/oracle.rs:29-37): `polynomials`, one LDE matrix per group of equal degree, the
+ * batch tree's digests and cap.  HOST pointers; these calls join the busy guard (see the prover session section):
+ * p2hot_batch_oracle_commit / _coeffs / _rows / _paths / _digests and p2hot_batch_prove_openings.  p2hot_batch_oracle_free follows
+ * the rules of p2hot_batch_free. */
+typedef struct p2hot_batch_oracle p2hot_batch_oracle;
+/* BatchFriOracle::from_values (is_values != 0, oracle.rs:44-66) / from_coeffs (:69-125), blinding = false.
+ *   cols        W host pointers, polynomial c has 2^log_n[c] words; log_n non-increasing (the reference's assert, :81), consecutive
+ *               polynomials of equal degree form a group
+ *   coeffs_out  NULL or a TABLE of W host pointers (as P2HOT_COEFFS_PER_COLUMN): polynomial c's coefficients go to table[c]
+ *   digests_out [p2hot_num_digests(log_n[0] + rate_bits, cap_height)][4], cap_out [2^cap_height][4]: caller-allocated or NULL
+ *   flags       0 (hasher bits other than 0: P2HOT_EUNSUPPORTED; anything else: P2HOT_EINVAL)
+ * P2HOT_EINVAL: W = 0, degrees out of order, cap_height above the smallest LDE height log_n[W-1] + rate_bits. */
+int p2hot_batch_oracle_commit(p2hot_ctx *ctx, const uint64_t *const *cols, const unsigned *log_n, size_t W, unsigned rate_bits,
+                              unsigned cap_height, int is_values, unsigned flags, uint64_t *coeffs_out, uint64_t *digests_out,
+                              uint64_t *cap_out, p2hot_batch_oracle **handle_out);
+size_t p2hot_batch_oracle_num_groups(const p2hot_batch_oracle *oracle);
+/* width (polynomials) and degree log of group j */
+int p2hot_batch_oracle_group_info(const p2hot_batch_oracle *oracle, size_t group, size_t *width_out, unsigned *degree_log_out);
+/* `polynomials[first .. first + count)` in commit order, canonical, back to back (each with its own length) */
+int p2hot_batch_oracle_coeffs(p2hot_batch_oracle *oracle, size_t first, size_t count, uint64_t *out);
+/* BatchMerkleTree::values flattened for m leaf indices of the tallest group: out [m][sum_j W_j] */
+int p2hot_batch_oracle_rows(p2hot_batch_oracle *oracle, const uint64_t *row_idx, size_t m, uint64_t *out);
+/* BatchMerkleTree::open_batch: out [m][log_n[0] + rate_bits - cap_height][4] */
+int p2hot_batch_oracle_paths(p2hot_batch_oracle *oracle, const uint64_t *leaf_idx, size_t m, uint64_t *out);
+/* batch_merkle_tree.digests: out [p2hot_num_digests(log_n[0] + rate_bits, cap_height)][4] */
+int p2hot_batch_oracle_digests(p2hot_batch_oracle *oracle, uint64_t *out);
+void p2hot_batch_oracle_free(p2hot_batch_oracle *oracle);
+/* FriInstanceInfo::batches (fri/structure.rs) of one instance = one degree; poly_index counts the oracle's polynomials in commit order */
+typedef struct p2hot_fri_instance { const p2hot_fri_batch_info *batches; size_t n_batches; } p2hot_fri_instance;
+/* the p2hot_fri_proof layout of p2hot_batch_prove_openings: initial_leaves [Q][sum_o sum_j W_{o,j}], initial_paths
+ * [Q][n_oracles][h_0 - cap_height][4], the rest as p2hot_fri_proof_sizes with the first oracle's largest degree.  No context, so no
+ * error text; the sizes hold only for oracles p2hot_batch_prove_openings accepts together (one context, rate, cap height and tallest
+ * height): it is that call which checks them. */
+int p2hot_batch_fri_proof_sizes(const p2hot_batch_oracle *const *oracles, size_t n_oracles, const p2hot_fri_params *params,
+                                p2hot_fri_proof_layout *out);
+/* BatchFriOracle::prove_openings (batch_fri/oracle.rs:128-192) + batch_fri_proof (batch_fri/prover.rs:25-86): alpha once, one
+ * final_poly per instance (the prelude of p2hot_prove_openings per degree), the batch commit phase, the grind (smallest witness),
+ * the query rounds over the batch trees (:175-217); one synchronisation, the challenges stay on the device.
+ * Validated before anything is enqueued (the context stays usable).  P2HOT_EINVAL: n_instances = 0; degree_bits not strictly
+ * decreasing; an oracle of another context, or whose tallest group is not 2^(degree_bits[0] + rate_bits) rows, or committed with
+ * another rate / cap height; a polynomial opened by instance i whose degree is not 2^degree_bits[i]; an instance whose length is not
+ * reached exactly after some round; a round tree smaller than the cap; non-zero max_num_query_steps or final_poly_coeff_len.
+ * P2HOT_EUNSUPPORTED: a Keccak challenger. */
+int p2hot_batch_prove_openings(p2hot_ctx *ctx, const unsigned *degree_bits, const p2hot_fri_instance *instances, size_t n_instances,
+                               const p2hot_batch_oracle *const *oracles, size_t n_oracles, p2hot_challenger *challenger,
+                               const p2hot_fri_params *params, p2hot_fri_proof *proof);
 
 /* ================================================================ multi-GPU: the coset-sharded commit
  * The rate-1/B LDE is B independent coset transforms and coset j is the contiguous row block bitrev(j) of the

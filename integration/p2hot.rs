@@ -96,6 +96,10 @@ pub struct P2hotCols {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct P2hotBatchOracle {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct P2hotComm {
     _private: [u8; 0],
 }
@@ -204,6 +208,13 @@ pub struct P2hotGateSet {
     pub num_selectors: u32,
     pub num_lookup_selectors: u32,
     pub public_inputs_hash: [u64; 4],
+}
+
+/// p2hot_fri_instance: the batches of one FriInstanceInfo (fri/structure.rs) of a batch FRI proof, one instance per degree
+#[repr(C)]
+pub struct P2hotFriInstance {
+    pub batches: *const P2hotFriBatchInfo,
+    pub n_batches: usize,
 }
 
 /// p2hot_allgather_fn
@@ -409,6 +420,46 @@ extern "C" {
         gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gate_sums: *const *const u64, num_lu_slots: c_uint, num_lut_slots: c_uint,
         num_luts: c_uint, lookup_selectors_first_col: usize, deltas: *const u64, lut_re_poly_evals: *const u64, gates: *const P2hotGateSet,
         values_out: *mut u64, chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
+    // ---- batch FRI (batch_fri/{oracle,prover}.rs, hash/batch_merkle_tree.rs); not hooked into the patched crate yet
+    pub fn p2hot_batch_merkle_dev(
+        ctx: *mut P2hotCtx, d_groups: *const *const u64, strides: *const usize, widths: *const usize, log_heights: *const c_uint,
+        n_groups: usize, cap_height: c_uint, d_digests: *mut u64, d_cap: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_batch_merkle_rows_dev(
+        ctx: *mut P2hotCtx, d_groups: *const *const u64, strides: *const usize, widths: *const usize, log_heights: *const c_uint,
+        n_groups: usize, d_idx: *const u64, m: usize, d_out: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_batch_merkle_paths_dev(
+        ctx: *mut P2hotCtx, d_digests: *const u64, log_heights: *const c_uint, n_groups: usize, cap_height: c_uint, d_idx: *const u64,
+        m: usize, d_out: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_batch_fri_commit_dev(
+        ctx: *mut P2hotCtx, d_coeffs_planar: *const *const u64, log_n: *const c_uint, n_instances: usize, rate_bits: c_uint,
+        cap_height: c_uint, arity_bits: *const c_uint, n_rounds: c_uint, challenger: *mut P2hotChallenger, d_leaves_out: *mut u64,
+        digests_out: *mut u64, digests_on_device: c_int, caps_out: *mut u64, betas_out: *mut u64, final_out: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_batch_oracle_commit(
+        ctx: *mut P2hotCtx, cols: *const *const u64, log_n: *const c_uint, W: usize, rate_bits: c_uint, cap_height: c_uint,
+        is_values: c_int, flags: c_uint, coeffs_out: *mut u64, digests_out: *mut u64, cap_out: *mut u64,
+        handle_out: *mut *mut P2hotBatchOracle,
+    ) -> c_int;
+    pub fn p2hot_batch_oracle_num_groups(oracle: *const P2hotBatchOracle) -> usize;
+    pub fn p2hot_batch_oracle_group_info(
+        oracle: *const P2hotBatchOracle, group: usize, width_out: *mut usize, degree_log_out: *mut c_uint,
+    ) -> c_int;
+    pub fn p2hot_batch_oracle_coeffs(oracle: *mut P2hotBatchOracle, first: usize, count: usize, out: *mut u64) -> c_int;
+    pub fn p2hot_batch_oracle_rows(oracle: *mut P2hotBatchOracle, row_idx: *const u64, m: usize, out: *mut u64) -> c_int;
+    pub fn p2hot_batch_oracle_paths(oracle: *mut P2hotBatchOracle, leaf_idx: *const u64, m: usize, out: *mut u64) -> c_int;
+    pub fn p2hot_batch_oracle_digests(oracle: *mut P2hotBatchOracle, out: *mut u64) -> c_int;
+    pub fn p2hot_batch_oracle_free(oracle: *mut P2hotBatchOracle);
+    pub fn p2hot_batch_fri_proof_sizes(
+        oracles: *const *const P2hotBatchOracle, n_oracles: usize, params: *const P2hotFriParams, out: *mut P2hotFriProofLayout,
+    ) -> c_int;
+    pub fn p2hot_batch_prove_openings(
+        ctx: *mut P2hotCtx, degree_bits: *const c_uint, instances: *const P2hotFriInstance, n_instances: usize,
+        oracles: *const *const P2hotBatchOracle, n_oracles: usize, challenger: *mut P2hotChallenger, params: *const P2hotFriParams,
+        proof: *mut P2hotFriProof,
     ) -> c_int;
     // ---- multi-GPU
     pub fn p2hot_comm_unique_id(out: *mut u8) -> c_int;

@@ -56,6 +56,10 @@ class FriProofLayout(C.Structure):  # p2hot_fri_proof_layout
                 ("step_evals_words", sz), ("step_paths_words", sz)]
 
 
+class FriInstance(C.Structure):  # p2hot_fri_instance
+    _fields_ = [("batches", C.POINTER(FriBatchInfo)), ("n_batches", sz)]
+
+
 # p2hot_allgather_fn: (user, d_base, offsets, world, bytes, hip_stream) -> int
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.POINTER(sz), C.c_int, sz, vp)
 
@@ -146,6 +150,21 @@ SIGNATURES = {
     "p2hot_quotient_polys_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), vp, vp, C.POINTER(vp)]),
     "p2hot_quotient_polys_lookup_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), u, u, u, sz, vp, vp, vp, vp,
                                               C.POINTER(vp)]),
+    "p2hot_batch_merkle_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, u, vp, vp]),
+    "p2hot_batch_merkle_rows_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, vp, sz, vp]),
+    "p2hot_batch_merkle_paths_dev": (i, [vp, vp, C.POINTER(u), sz, u, vp, sz, vp]),
+    "p2hot_batch_fri_commit_dev": (i, [vp, C.POINTER(vp), C.POINTER(u), sz, u, u, C.POINTER(u), u, vp, vp, vp, i, vp, vp, vp]),
+    "p2hot_batch_oracle_commit": (i, [vp, C.POINTER(vp), C.POINTER(u), sz, u, u, i, u, vp, vp, vp, C.POINTER(vp)]),
+    "p2hot_batch_oracle_num_groups": (sz, [vp]),
+    "p2hot_batch_oracle_group_info": (i, [vp, sz, C.POINTER(sz), C.POINTER(u)]),
+    "p2hot_batch_oracle_coeffs": (i, [vp, sz, sz, vp]),
+    "p2hot_batch_oracle_rows": (i, [vp, vp, sz, vp]),
+    "p2hot_batch_oracle_paths": (i, [vp, vp, sz, vp]),
+    "p2hot_batch_oracle_digests": (i, [vp, vp]),
+    "p2hot_batch_oracle_free": (None, [vp]),
+    "p2hot_batch_fri_proof_sizes": (i, [C.POINTER(vp), sz, C.POINTER(FriParams), C.POINTER(FriProofLayout)]),
+    "p2hot_batch_prove_openings": (i, [vp, C.POINTER(u), C.POINTER(FriInstance), sz, C.POINTER(vp), sz, vp, C.POINTER(FriParams),
+                                       C.POINTER(FriProof)]),
     "p2hot_comm_unique_id": (i, [vp]),
     "p2hot_comm_create_rccl": (i, [vp, i, i, vp, C.POINTER(vp)]),
     "p2hot_comm_create_callback": (i, [vp, i, i, ALLGATHER_FN, vp, C.POINTER(vp)]),

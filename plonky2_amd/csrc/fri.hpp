@@ -575,4 +575,107 @@ __global__ void __launch_bounds__(256) pow_kernel_k256(const Challenger *ch, uns
     if (lz >= pow_bits) atomicMin(best, (unsigned long long)cand);
 }
 
+// ---- batch FRI (plonky2/src/batch_fri/prover.rs, hash/batch_merkle_tree.rs) ----
+// fold_kernel for a round after which the next instance joins (batch_fri/prover.rs:115-136): the reference evaluates the folded
+// coefficients f on shift' * H, adds the joining codeword (P's values on g * H) index by index, times beta for f, and interpolates
+// on shift' * H again.  P(g w^i) = P'(shift' w^i) for P'(X) = P(X g / shift'), and both polynomials have fewer coefficients than
+// the coset has points, so the interpolant is coefficient by coefficient
+//   s_k = beta * f_k + p_k * c^k,   c = g / shift'  (a base-field constant of the round)
+// c^k by square-and-multiply per lane: the base is wave-uniform, the exponent is the lane's coefficient index.
+__global__ void __launch_bounds__(256) fold_join_kernel(const u64 *c0, const u64 *c1, unsigned arity_bits, const u64 *beta, size_t m_out,
+                                                        const u64 *p0, const u64 *p1, u64 c, u64 *o0, u64 *o1) {
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m_out) return;
+    gl::ext2 b{beta[0], beta[1]};
+    gl::ext2 acc{0, 0};
+    const size_t base = j << arity_bits;
+    for (unsigned i = 1u << arity_bits; i-- > 0;) {
+        acc = gl::ext_mul(acc, b);
+        acc.a0 = gl::add(acc.a0, c0[base + i]);
+        acc.a1 = gl::add(acc.a1, c1[base + i]);
+    }
+    acc = gl::ext_mul(acc, b);
+    const u64 ck = gl::pow(c, (u64)j);
+    o0[j] = gl::canon(gl::add(acc.a0, gl::mul(p0[j], ck)));
+    o1[j] = gl::canon(gl::add(acc.a1, gl::mul(p1[j], ck)));
+}
+
+// A BatchMerkleTree as the query phase sees it, by value (at most 8 groups).  Group k: its column-major LDE matrix, the shift from
+// a leaf index of the tallest group to its own row (h_0 - h_k), its first word inside values(i) flattened; segment k of the digest
+// array: where it starts, its leaf and cap heights (h_k, h_{k+1} or the tree's cap height), its first layer inside open_batch(i).
+struct BatchTreeTable {
+    const u64 *lde[8];
+    size_t stride[8];
+    size_t dig_off[8];  // in digests
+    unsigned w_off[8], shift[8], log_h[8], cap_h[8], layer_off[8];
+    unsigned n_groups, total_w, layers;
+};
+
+// BatchMerkleTree::values (hash/batch_merkle_tree.rs:155-164) flattened, for m leaf indices of the tallest group:
+// out[q][w_off[k] + c] = group k's element (idx[q] >> shift[k], c).  Lane = (query, word).  The group is picked by compares against
+// constants of the table (no dynamically indexed array).  An index >= 2^log_h[0] zeroes its row and raises *oob like gather_rows_kernel.
+__global__ void __launch_bounds__(256) batch_rows_kernel(BatchTreeTable t, const u64 *idx, size_t m, u64 *out, unsigned *oob) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m * t.total_w) return;
+    const size_t q = e / t.total_w;
+    const unsigned c = (unsigned)(e % t.total_w);
+    const u64 r = idx[q];
+    if (r >> t.log_h[0]) {
+        out[e] = 0;
+        if (c == 0) atomicOr(oob, 1u);
+        return;
+    }
+    const u64 *lde = t.lde[0];
+    size_t stride = t.stride[0];
+    unsigned w0 = 0, sh = 0;
+#pragma unroll
+    for (unsigned k = 1; k < 8; ++k)
+        if (k < t.n_groups && c >= t.w_off[k]) {
+            lde = t.lde[k];
+            stride = t.stride[k];
+            w0 = t.w_off[k];
+            sh = t.shift[k];
+        }
+    out[e] = gl::canon(lde[(size_t)(c - w0) * stride + (size_t)(r >> sh)]);
+}
+
+// BatchMerkleTree::open_batch (hash/batch_merkle_tree.rs:133-153): the merkle_tree_prove paths of the segments, concatenated.
+// out[q][i] = sibling at layer i of leaf idx[q]; layer i belongs to the last segment k with layer_off[k] <= i and is layer
+// i - layer_off[k] of the tree (2^log_h[k] leaves, cap height cap_h[k]) at digests + 4 * dig_off[k], for leaf idx[q] >> shift[k].
+// Lane = (query, layer), as merkle_paths_kernel.
+__global__ void __launch_bounds__(256) batch_paths_kernel(const u64 *digests, BatchTreeTable t, const u64 *idx, size_t m, u64 *out,
+                                                          unsigned *oob) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t.layers == 0 || e >= m * t.layers) return;
+    const size_t q = e / t.layers;
+    const unsigned i = (unsigned)(e % t.layers);
+    const u64 r = idx[q];
+    if (r >> t.log_h[0]) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) out[4 * e + w] = 0;
+        if (i == 0) atomicOr(oob, 2u);
+        return;
+    }
+    size_t dig_off = t.dig_off[0];
+    unsigned l0 = 0, sh = 0, lh = t.log_h[0], ch = t.cap_h[0];
+#pragma unroll
+    for (unsigned k = 1; k < 8; ++k)
+        if (k < t.n_groups && i >= t.layer_off[k]) {
+            dig_off = t.dig_off[k];
+            l0 = t.layer_off[k];
+            sh = t.shift[k];
+            lh = t.log_h[k];
+            ch = t.cap_h[k];
+        }
+    const unsigned layers = lh - ch, il = i - l0;
+    const size_t leaf = (size_t)(r >> sh);
+    const size_t tree_len = 2 * (((size_t)1 << layers) - 1);
+    const size_t pair = (leaf & (((size_t)1 << layers) - 1)) >> il;
+    const size_t parity = pair & 1;
+    const size_t siblings_index = ((pair >> 1) << (il + 1)) + ((size_t)1 << il) - 1;
+    const u64 *src = digests + 4 * (dig_off + tree_len * (leaf >> layers) + 2 * siblings_index + (1 - parity));
+#pragma unroll
+    for (int w = 0; w < 4; ++w) out[4 * e + w] = src[w];
+}
+
 }  // namespace fri

@@ -39,6 +39,18 @@ struct FriPlanarReader {  // element (L, e) = plane[e & 1][(L << arity_bits) + (
     }
 };
 
+// A leaf of an inner segment of a BatchMerkleTree (hash/batch_merkle_tree.rs:85-94): digest L of the layer below (the previous
+// segment's cap array, 4 words per entry) followed by row L of the group's column-major LDE matrix.  W of the kernels is 4 + the
+// group's width, so such a leaf is hashed whenever the group has a column (hash_or_noop copies only a leaf of 4 words or fewer).
+struct DigestPrefixedReader {  // element (L, e) = e < 4 ? prefix[4 * L + e] : m[(e - 4) * stride + L]
+    const u64 *prefix;
+    const u64 *m;
+    size_t stride;
+    __device__ __forceinline__ u64 operator()(size_t L, unsigned e) const {
+        return e < 4 ? prefix[4 * L + e] : m[(size_t)(e - 4) * stride + L];
+    }
+};
+
 // where node j (global index over the forest of subtrees with 2^h leaves each) of `level` goes
 __device__ __forceinline__ u64 *node_slot(u64 *digests, u64 *cap, unsigned h, unsigned level, size_t j) {
     if (level == h) return cap + 4 * j;

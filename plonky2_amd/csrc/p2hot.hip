@@ -89,7 +89,7 @@ struct p2hot_ctx {
     struct Scratch {
         void *p = nullptr;
         size_t cap = 0;
-    } scratch[4];  // 0: NTT temporary, 1: final_poly, 2: FRI commit phase, 3: all-gather staging of the sharded commit (grow-only, reused across calls)
+    } scratch[5];  // 0: NTT temporary, 1: final_poly, 2: FRI commit phase, 3: all-gather staging of the sharded commit, 4: the caps between the segments of a batch Merkle tree (grow-only, reused across calls)
     // coset scale tables keyed by (log_n, rate_bits, shift, first block, block count, first-pass log_r)
     std::map<std::tuple<unsigned, unsigned, u64, size_t, size_t, unsigned>, u64 *> scale_cache;
     std::map<std::tuple<int, unsigned, unsigned>, u64 *> twid_cache;  // (inverse, log_nblk, log_r) -> inter-pass twiddle table
@@ -1212,6 +1212,8 @@ static int hash_leaves_range(p2hot_ctx *ctx, hipStream_t stream, Reader rd, size
         if constexpr (std::is_same<Reader, merkle::FriPlanarReader>::value) {  // the round trees of a Keccak challenger's commit phase
             P2HOT_LAUNCH(fri::round_leaves_kernel_k256, dim3(cdiv(count, 256)), dim3(256), 0, stream, rd, (unsigned)W, leaf_offset, count,
                          g.h, hash_n, g.dig, g.cap);
+        } else if constexpr (std::is_same<Reader, merkle::DigestPrefixedReader>::value) {  // the inner segments of a batch tree
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "batch Merkle trees are Poseidon-only");
         } else {
             P2HOT_LAUNCH((keccak::keccak_leaves_kernel<Reader>), dim3(cdiv(count, 256)), dim3(256), 0, stream, rd, (unsigned)W,
                          leaf_offset, count, g.h, hash_n, g.dig, g.cap);
@@ -1587,6 +1589,14 @@ extern "C" int p2hot_challenger_step(p2hot_challenger *ch, const uint64_t *obser
 }
 
 // ------------------------------------------------------------------ FRI commit phase
+// batch FRI (batch_fri/prover.rs:124-135): the final polynomials that join the commit phase after a fold, as device planes
+// [2][2^log_n[j]] with strictly decreasing log_n, all below the first instance's (validated by the caller: batch_fri.hpp)
+struct BatchJoin {
+    const uint64_t *const *d_planar;
+    const unsigned *log_n;
+    size_t count;
+};
+
 // coeffs: host [n][2] interleaved, or (d_planar != NULL) device planes [2][n]
 // max_num_query_steps / final_poly_coeff_len: the Option<usize> arguments of fri_committed_trees (prover.rs:89-90), 0 = None
 static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_t *d_planar, unsigned log_n,
@@ -1594,7 +1604,7 @@ static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_
                            unsigned max_num_query_steps, size_t final_poly_coeff_len,
                            p2hot_challenger *challenger, uint64_t *leaves_out, bool leaves_on_device, uint64_t *digests_out,
                            bool digests_on_device, uint64_t *caps_out, uint64_t *betas_out, uint64_t *final_out,
-                           bool defer_sync = false) {
+                           bool defer_sync = false, const BatchJoin *join = nullptr) {
     if (!ctx || !challenger || challenger->ctx != ctx) return P2HOT_EINVAL;
     P2_TRY(check_log(ctx, log_n + rate_bits, "fri_commit"));
     if ((!coeffs && !d_planar) || (n_rounds && !arity_bits)) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit: null input");
@@ -1645,6 +1655,7 @@ static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_
         u64 shift = gl::COSET_SHIFT;
         size_t m = N;
         unsigned log_cur = log_n;
+        size_t joined = 0;
         for (unsigned r = 0; r < n_rounds; ++r) {
             const unsigned ab = arity_bits[r];
             // values = coeffs.lde(rate_bits).coset_fft(shift), rows in bit-reversed order
@@ -1684,8 +1695,16 @@ static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_
             }
             // prover.rs:111-118: fold the coefficients, shift <- shift^arity
             const size_t out_n = cur_n >> ab;
-            P2HOT_LAUNCH(fri::fold_kernel, dim3(cdiv(out_n, 256)), dim3(256), 0, ctx->stream, cur, cur + cur_n, ab,
-                         beta.u(), out_n, nxt, nxt + out_n);
+            if (join && joined < join->count && join->log_n[joined] == log_cur - ab) {
+                // batch_fri/prover.rs:122-136: the next instance has the folded length and joins; c = g / shift^arity
+                const u64 *p = join->d_planar[joined++];
+                const u64 c = gl::mul(gl::COSET_SHIFT, gl::inv(gl::pow(shift, (u64)1 << ab)));
+                P2HOT_LAUNCH(fri::fold_join_kernel, dim3(cdiv(out_n, 256)), dim3(256), 0, ctx->stream, cur, cur + cur_n, ab, beta.u(),
+                             out_n, p, p + out_n, c, nxt, nxt + out_n);
+            } else {
+                P2HOT_LAUNCH(fri::fold_kernel, dim3(cdiv(out_n, 256)), dim3(256), 0, ctx->stream, cur, cur + cur_n, ab,
+                             beta.u(), out_n, nxt, nxt + out_n);
+            }
             P2_LAUNCH_CHECK(ctx);
             u64 *t = cur;
             cur = nxt;
@@ -2089,3 +2108,4 @@ struct p2hot_cols {
 
 #include "host_prover.hpp"
 #include "host_multi.hpp"
+#include "batch_fri.hpp"
