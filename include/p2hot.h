@@ -280,7 +280,8 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * from the main thread, outside its rayon closures).  Serialised by the library (busy guard): p2hot_commit*, p2hot_cols_upload,
  * p2hot_batch_coeffs / _rows / _paths / _digests / _subgroup_values, p2hot_eval_openings, p2hot_prove_openings, p2hot_partial_products,
  * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_quotient_polys_lookup, p2hot_lookup_polys, p2hot_cols_concat, p2hot_gate_sums,
- * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_ctx_trim, p2hot_batch_oracle_commit,
+ * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_stark_lookup_polys, p2hot_stark_ctl_polys,
+ * p2hot_stark_quotient_polys, p2hot_ctx_trim, p2hot_batch_oracle_commit,
  * p2hot_batch_oracle_coeffs / _rows / _paths / _digests, p2hot_batch_prove_openings.  p2hot_batch_free / p2hot_batch_oracle_free / p2hot_cols_free may be called from any thread at any time (a
  * Drop, a finaliser): the block cache has its own lock.  Everything else -- the *_dev building blocks, p2hot_fri_commit,
  * p2hot_fri_pow, p2hot_challenger_* -- enqueues on the context's stream without a guard: the CALLER serialises those with
@@ -659,6 +660,86 @@ int p2hot_quotient_polys_lookup_gates(p2hot_ctx *ctx, const p2hot_batch *wires, 
                                       unsigned num_luts, size_t lookup_selectors_first_col, const uint64_t *deltas,
                                       const uint64_t *lut_re_poly_evals, const p2hot_gate_set *gates, uint64_t *values_out,
                                       p2hot_cols **chunks_out);
+
+/* ================================================================ starky: logUp lookups and cross-table lookups of one STARK table
+ * The stage of starky/src/prover.rs::prove_with_commitment between the trace commitment and the quotient commitment.  Poseidon
+ * configuration, single GPU: a KeccakHash commitment is P2HOT_EUNSUPPORTED, and the multi-GPU group has no entry point here.
+ *
+ * Descriptors.  The reference's Column (starky/src/lookup.rs:137-141: current-row terms, next-row terms, a constant) and Filter
+ * (lookup.rs:37-40: degree-2 products plus degree-1 constants) as flat HOST arrays the library uploads per call:
+ *   term     coeff * trace[col] of the current row (next = 0) or of the next row (next = 1)
+ *   column   terms [first_term, first_term + num_terms) plus `constant`
+ *   filter   sum of column[products[2 p]] * column[products[2 p + 1]] over p in [first_product, + num_products), plus the sum of
+ *            column[constants[k]] over k in [first_constant, + num_constants); Filter::default() is one constant-1 column
+ *   lookup   Lookup (lookup.rs:415-429): looking columns [first_column, + num_columns), their filters [first_filter, + num_columns),
+ *            the table column and the frequencies column (column ids)
+ *   looking  one (columns, filter) of a CTL Z (cross_table_lookup.rs:155-167): columns [first_column, + num_columns), a filter id
+ *   ctl_z    one CtlZData: looking entries [first_looking, + num_looking) and its GrandProductChallenge
+ * Evaluation: Column::eval_table (lookup.rs:324-335; next row = (i + 1) mod n) when the polynomials are generated,
+ * Column::eval_with_next (:306-321) for looking columns and filters in the quotient, Column::eval (:293-303, current-row terms
+ * ONLY) for the table and frequencies columns in the quotient (lookup.rs:851, :856).
+ * chunk = constraint_degree.checked_sub(1).unwrap_or(1) (lookup.rs:439, :670, :755); constraint_degree == 1 divides by zero in the
+ * reference and is P2HOT_EINVAL.  eval_helper_columns knows chunks of one or two columns only (lookup.rs:675-691, `todo!`): a lookup
+ * or a Z with a chunk of three or more is P2HOT_EUNSUPPORTED from all three entry points.
+ * P2HOT_EINVAL from all three, before anything is enqueued: a term's col beyond the trace's width; a term, column, filter or
+ * looking id beyond its array; a lookup with num_columns == 0 or a Z with num_looking == 0; num_challenges outside 1..4; null
+ * arrays with a nonzero count.  A zero col + x, table + x or combined v ("Tried to invert zero": the reference panics in
+ * batch_multiplicative_inverse) is P2HOT_EINVAL after the kernels ran. */
+typedef struct p2hot_stark_term { uint32_t col, next; uint64_t coeff; } p2hot_stark_term;
+typedef struct p2hot_stark_column { uint32_t first_term, num_terms; uint64_t constant; } p2hot_stark_column;
+typedef struct p2hot_stark_filter { uint32_t first_product, num_products, first_constant, num_constants; } p2hot_stark_filter;
+typedef struct p2hot_stark_lookup { uint32_t first_column, num_columns, first_filter, table_column, frequencies_column; } p2hot_stark_lookup;
+typedef struct p2hot_stark_looking { uint32_t first_column, num_columns, filter; } p2hot_stark_looking;
+typedef struct p2hot_stark_ctl_z { uint32_t first_looking, num_looking; uint64_t beta, gamma; } p2hot_stark_ctl_z;
+typedef struct p2hot_stark_tables { const p2hot_stark_term *terms; const p2hot_stark_column *columns; const uint32_t *products;
+                                    const uint32_t *constants; const p2hot_stark_filter *filters; const p2hot_stark_looking *looking;
+                                    uint32_t num_terms, num_columns, num_products, num_constants, num_filters, num_looking; } p2hot_stark_tables;
+/* lookup_helper_columns (starky/src/lookup.rs:579-652) for every lookup and every challenge, in the order of
+ * starky/src/prover.rs:177-195: per lookup, per challenge x, the helper columns h_0 .. h_{H-1}, H = ceil(num_columns / chunk), then Z:
+ *   h_k[i] = sum_{c in chunk k} filter_c(i) / (col_c(i) + x),  Z[0] = 0,  Z[i+1] = Z[i] + sum_k h_k[i] - freq(i) / (table(i) + x)
+ * (1 / (table + x) is not an output column, whatever lookup.rs:433-436 says).
+ *   trace       device-resident column set, 2^k rows
+ *   challenges  HOST [num_challenges]
+ *   out_host    [sum_l num_challenges (H_l + 1)][n] and / or out_cols (ready for p2hot_cols_concat / p2hot_commit_cols) */
+int p2hot_stark_lookup_polys(p2hot_ctx *ctx, const p2hot_cols *trace, const p2hot_stark_tables *tables, const p2hot_stark_lookup *lookups,
+                             unsigned num_lookups, const uint64_t *challenges, unsigned num_challenges, unsigned constraint_degree,
+                             uint64_t *out_host, p2hot_cols **out_cols);
+/* partial_sums (starky/src/cross_table_lookup.rs:383-414) for every CTL Z of one table, in get_ctl_auxiliary_polys' order
+ * (cross_table_lookup.rs:253-261): the helper columns of all Zs in the order given, then all Zs.  For a Z with entries e:
+ *   v_e(i) = sum_j col_{e,j}(i) beta^j + gamma (GrandProductChallenge::combine, lookup.rs:457-464),
+ *   h_k = sum_{e in chunk k} filter_e / v_e,  Z[n-1] = sum_k h_k[n-1],  Z[i] = Z[i+1] + sum_k h_k[i]
+ * and a Z with ONE entry has no helper column: its Z sums filter / v directly (cross_table_lookup.rs:407-411).
+ *   zs_first    NULL or HOST [num_zs]: Z[0] of every Z (StarkOpeningSet::ctl_zs_first, starky/src/proof.rs)
+ * Which Z belongs to which table (cross_table_lookup_data's group_by, cross_table_lookup.rs:270-339) is the caller's bookkeeping. */
+int p2hot_stark_ctl_polys(p2hot_ctx *ctx, const p2hot_cols *trace, const p2hot_stark_tables *tables, const p2hot_stark_ctl_z *ctl_zs,
+                          unsigned num_zs, unsigned constraint_degree, uint64_t *out_host, p2hot_cols **out_cols, uint64_t *zs_first);
+/* compute_quotient_polys (starky/src/prover.rs:488-671) without Stark::eval_packed_generic: the terms of
+ * eval_packed_lookups_generic (lookup.rs:804-863) and eval_cross_table_lookup_checks (cross_table_lookup.rs:558-629) at every
+ * point x = g w^i of the coset of size n << qbits, qdf = max(1, constraint_degree - 1), qbits = log2_ceil(qdf) (prover.rs:516),
+ * local row = get_lde_values(i, step), next row = index (i + 2^qbits) mod size (prover.rs:521-523, :552).
+ *   trace, aux        commitments of this context with the same degree and rate; aux (NULL when there are neither lookups nor
+ *                     CTLs) holds exactly the lookup columns (p2hot_stark_lookup_polys' order), then the CTL helpers, then the CTL Zs
+ *   ctl_num_helpers   HOST [num_ctl_zs]: the helper columns of every Z in aux (CtlData::num_ctl_helper_polys), or NULL for what
+ *                     p2hot_stark_ctl_polys produces.  0 or ceil(num_looking / chunk); 0 with more than two entries is P2HOT_EINVAL
+ *   alphas            HOST [num_challenges]; the lookup challenges are num_challenges many too (StarkConfig::num_challenges)
+ *   constraint_accs   NULL or [num_challenges] HOST pointers to n << qbits words, natural order: ConstraintConsumer::accumulators()
+ *                     after stark.eval_packed_generic alone (the STARK's own constraints stay the caller's)
+ * The consumer is a Horner in alpha (constraint_consumer.rs:68-74) and the STARK's constraints come first (vanishing_poly.rs), so
+ * with K library terms c_0 .. c_{K-1} in the consumer's order -- per lookup and challenge the helper checks, constraint_first_row(z),
+ * constraint((next_z - z)(t + x) - y); per Z the helper checks, constraint_last_row, constraint_transition in the three branches of
+ * cross_table_lookup.rs:604-627 --
+ *   value_a(x) = (constraint_accs[a][i] alpha_a^K + sum_t c_t alpha_a^(K-1-t)) / Z_H(x)
+ * with z_last = x - w_n^-1, L_first(x) = Z_H(x) / (n (x - 1)), L_last(x) = Z_H(x) / (n (w_n x - 1)) (the values of the selector
+ * LDEs of prover.rs:526-529).  values_out / chunks_out as in p2hot_quotient_polys (coset_ifft, trim to qdf n, chunks of n;
+ * "Quotient has failed" is P2HOT_EINVAL).  constraint_degree 0 is taken as qdf = 1 (the subtraction saturates, as the chunk
+ * size does; Stark::quotient_degree_factor answers 0 there and the reference computes no quotient, prover.rs:508-510), so the three
+ * entry points accept the same degrees.  P2HOT_EINVAL besides the common cases: qbits > rate_bits, an aux
+ * whose column count is not exactly what the descriptors imply, commitments of another context, degree or rate. */
+int p2hot_stark_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *trace, const p2hot_batch *aux, const p2hot_stark_tables *tables,
+                               const p2hot_stark_lookup *lookups, unsigned num_lookups, const uint64_t *lookup_challenges,
+                               const p2hot_stark_ctl_z *ctl_zs, unsigned num_ctl_zs, const unsigned *ctl_num_helpers,
+                               unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges,
+                               const uint64_t *const *constraint_accs, uint64_t *values_out, p2hot_cols **chunks_out);
 
 /* ================================================================ batch FRI: polynomials of several degrees, one tree, one proof
  * plonky2/src/batch_fri/{oracle,prover}.rs over hash/batch_merkle_tree.rs.  Poseidon configuration, one GPU, blinding = false: a

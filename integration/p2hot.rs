@@ -217,6 +217,82 @@ pub struct P2hotFriInstance {
     pub n_batches: usize,
 }
 
+/// p2hot_stark_term: `coeff * trace[col]` of the current row (`next = 0`) or of the next row (`next = 1`) of a starky `Column`
+/// (starky/src/lookup.rs:137-141)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotStarkTerm {
+    pub col: u32,
+    pub next: u32,
+    pub coeff: u64,
+}
+
+/// p2hot_stark_column: the terms `[first_term, first_term + num_terms)` plus a constant
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotStarkColumn {
+    pub first_term: u32,
+    pub num_terms: u32,
+    pub constant: u64,
+}
+
+/// p2hot_stark_filter: a starky `Filter` (lookup.rs:37-40) as ranges of the product pairs and of the constant column ids
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotStarkFilter {
+    pub first_product: u32,
+    pub num_products: u32,
+    pub first_constant: u32,
+    pub num_constants: u32,
+}
+
+/// p2hot_stark_lookup: a starky `Lookup` (lookup.rs:415-429)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotStarkLookup {
+    pub first_column: u32,
+    pub num_columns: u32,
+    pub first_filter: u32,
+    pub table_column: u32,
+    pub frequencies_column: u32,
+}
+
+/// p2hot_stark_looking: one (columns, filter) of a `CtlZData` (cross_table_lookup.rs:155-167)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotStarkLooking {
+    pub first_column: u32,
+    pub num_columns: u32,
+    pub filter: u32,
+}
+
+/// p2hot_stark_ctl_z: one `CtlZData`: its looking entries and its `GrandProductChallenge`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotStarkCtlZ {
+    pub first_looking: u32,
+    pub num_looking: u32,
+    pub beta: u64,
+    pub gamma: u64,
+}
+
+/// p2hot_stark_tables: the flat descriptor arrays the three starky entry points read
+#[repr(C)]
+pub struct P2hotStarkTables {
+    pub terms: *const P2hotStarkTerm,
+    pub columns: *const P2hotStarkColumn,
+    pub products: *const u32,
+    pub constants: *const u32,
+    pub filters: *const P2hotStarkFilter,
+    pub looking: *const P2hotStarkLooking,
+    pub num_terms: u32,
+    pub num_columns: u32,
+    pub num_products: u32,
+    pub num_constants: u32,
+    pub num_filters: u32,
+    pub num_looking: u32,
+}
+
 /// p2hot_allgather_fn
 pub type P2hotAllgatherFn = Option<
     unsafe extern "C" fn(user: *mut c_void, d_base: *mut c_void, offsets: *const usize, world: c_int, bytes: usize, hip_stream: *mut c_void) -> c_int,
@@ -404,6 +480,20 @@ extern "C" {
         chunks_out: *mut *mut P2hotCols,
     ) -> c_int;
     pub fn p2hot_cols_concat(ctx: *mut P2hotCtx, a: *const P2hotCols, b: *const P2hotCols, out: *mut *mut P2hotCols) -> c_int;
+    pub fn p2hot_stark_lookup_polys(
+        ctx: *mut P2hotCtx, trace: *const P2hotCols, tables: *const P2hotStarkTables, lookups: *const P2hotStarkLookup, num_lookups: c_uint,
+        challenges: *const u64, num_challenges: c_uint, constraint_degree: c_uint, out_host: *mut u64, out_cols: *mut *mut P2hotCols,
+    ) -> c_int;
+    pub fn p2hot_stark_ctl_polys(
+        ctx: *mut P2hotCtx, trace: *const P2hotCols, tables: *const P2hotStarkTables, ctl_zs: *const P2hotStarkCtlZ, num_zs: c_uint,
+        constraint_degree: c_uint, out_host: *mut u64, out_cols: *mut *mut P2hotCols, zs_first: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_stark_quotient_polys(
+        ctx: *mut P2hotCtx, trace: *const P2hotBatch, aux: *const P2hotBatch, tables: *const P2hotStarkTables, lookups: *const P2hotStarkLookup,
+        num_lookups: c_uint, lookup_challenges: *const u64, ctl_zs: *const P2hotStarkCtlZ, num_ctl_zs: c_uint, ctl_num_helpers: *const c_uint,
+        constraint_degree: c_uint, alphas: *const u64, num_challenges: c_uint, constraint_accs: *const *const u64, values_out: *mut u64,
+        chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
     pub fn p2hot_gate_sums(
         ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize, gates: *const P2hotGateSet,
         quotient_degree_factor: c_uint, alphas: *const u64, num_challenges: c_uint, out_host: *mut u64,

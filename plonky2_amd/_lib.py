@@ -60,6 +60,36 @@ class FriInstance(C.Structure):  # p2hot_fri_instance
     _fields_ = [("batches", C.POINTER(FriBatchInfo)), ("n_batches", sz)]
 
 
+class StarkTerm(C.Structure):  # p2hot_stark_term
+    _fields_ = [("col", C.c_uint32), ("next", C.c_uint32), ("coeff", u64)]
+
+
+class StarkColumn(C.Structure):  # p2hot_stark_column
+    _fields_ = [("first_term", C.c_uint32), ("num_terms", C.c_uint32), ("constant", u64)]
+
+
+class StarkFilter(C.Structure):  # p2hot_stark_filter
+    _fields_ = [(name, C.c_uint32) for name in ("first_product", "num_products", "first_constant", "num_constants")]
+
+
+class StarkLookup(C.Structure):  # p2hot_stark_lookup
+    _fields_ = [(name, C.c_uint32) for name in ("first_column", "num_columns", "first_filter", "table_column", "frequencies_column")]
+
+
+class StarkLooking(C.Structure):  # p2hot_stark_looking
+    _fields_ = [(name, C.c_uint32) for name in ("first_column", "num_columns", "filter")]
+
+
+class StarkCtlZ(C.Structure):  # p2hot_stark_ctl_z
+    _fields_ = [("first_looking", C.c_uint32), ("num_looking", C.c_uint32), ("beta", u64), ("gamma", u64)]
+
+
+class StarkTables(C.Structure):  # p2hot_stark_tables
+    _fields_ = [("terms", C.POINTER(StarkTerm)), ("columns", C.POINTER(StarkColumn)), ("products", C.POINTER(C.c_uint32)),
+                ("constants", C.POINTER(C.c_uint32)), ("filters", C.POINTER(StarkFilter)), ("looking", C.POINTER(StarkLooking))] + \
+               [(name, C.c_uint32) for name in ("num_terms", "num_columns", "num_products", "num_constants", "num_filters", "num_looking")]
+
+
 # p2hot_allgather_fn: (user, d_base, offsets, world, bytes, hip_stream) -> int
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.POINTER(sz), C.c_int, sz, vp)
 
@@ -150,6 +180,9 @@ SIGNATURES = {
     "p2hot_quotient_polys_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), vp, vp, C.POINTER(vp)]),
     "p2hot_quotient_polys_lookup_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), u, u, u, sz, vp, vp, vp, vp,
                                               C.POINTER(vp)]),
+    "p2hot_stark_lookup_polys": (i, [vp, vp, vp, vp, u, vp, u, u, vp, C.POINTER(vp)]),
+    "p2hot_stark_ctl_polys": (i, [vp, vp, vp, vp, u, u, vp, C.POINTER(vp), vp]),
+    "p2hot_stark_quotient_polys": (i, [vp, vp, vp, vp, vp, u, vp, vp, u, vp, u, vp, u, C.POINTER(vp), vp, C.POINTER(vp)]),
     "p2hot_batch_merkle_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, u, vp, vp]),
     "p2hot_batch_merkle_rows_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, vp, sz, vp]),
     "p2hot_batch_merkle_paths_dev": (i, [vp, vp, C.POINTER(u), sz, u, vp, sz, vp]),

@@ -1,11 +1,12 @@
 // p2hot.hip -- context, pass planning and the C ABI of libp2hot (see include/p2hot.h).
-// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / gates.hpp / gates_recursion.hpp.
+// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / stark.hpp / gates.hpp / gates_recursion.hpp.
 #include "../../include/p2hot.h"
 
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <set>
 #include <mutex>
@@ -17,6 +18,7 @@
 #include "fri.hpp"
 #include "plonk.hpp"
 #include "lookup.hpp"
+#include "stark.hpp"
 #include "gates.hpp"
 #include "gates_recursion.hpp"
 #include "merkle.hpp"
@@ -2107,5 +2109,6 @@ struct p2hot_cols {
 };
 
 #include "host_prover.hpp"
+#include "host_stark.hpp"
 #include "host_multi.hpp"
 #include "batch_fri.hpp"
