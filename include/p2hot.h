@@ -281,7 +281,7 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * p2hot_batch_coeffs / _rows / _paths / _digests / _subgroup_values, p2hot_eval_openings, p2hot_prove_openings, p2hot_partial_products,
  * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_quotient_polys_lookup, p2hot_lookup_polys, p2hot_cols_concat, p2hot_gate_sums,
  * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_stark_lookup_polys, p2hot_stark_ctl_polys,
- * p2hot_stark_quotient_polys, p2hot_ctx_trim, p2hot_batch_oracle_commit,
+ * p2hot_stark_quotient_polys, p2hot_stark_constraint_accs, p2hot_stark_quotient_polys_air, p2hot_ctx_trim, p2hot_batch_oracle_commit,
  * p2hot_batch_oracle_coeffs / _rows / _paths / _digests, p2hot_batch_prove_openings.  p2hot_batch_free / p2hot_batch_oracle_free / p2hot_cols_free may be called from any thread at any time (a
  * Drop, a finaliser): the block cache has its own lock.  Everything else -- the *_dev building blocks, p2hot_fri_commit,
  * p2hot_fri_pow, p2hot_challenger_* -- enqueues on the context's stream without a guard: the CALLER serialises those with
@@ -740,6 +740,58 @@ int p2hot_stark_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *trace, const p
                                const p2hot_stark_ctl_z *ctl_zs, unsigned num_ctl_zs, const unsigned *ctl_num_helpers,
                                unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges,
                                const uint64_t *const *constraint_accs, uint64_t *values_out, p2hot_cols **chunks_out);
+
+/* ---------------------------------------------------------------- starky: the STARK's own constraints as a constraint program
+ * Stark::eval_packed_generic (starky/src/stark.rs) is user code; here it arrives as data: a straight-line program over the
+ * evaluation frame, flat HOST arrays the library uploads per call, interpreted at every point of the quotient coset (csrc/air.hpp).
+ * An operand (a, b) carries its kind in the top 3 bits and an index in the low 29:
+ *   P2HOT_AIR_LOCAL   trace column of the local row, get_lde_values(i, step)
+ *   P2HOT_AIR_NEXT    trace column of the row at (i + 2^qbits) mod size (prover.rs:552, :568-572)
+ *   P2HOT_AIR_PUBLIC  index into the call's public_inputs
+ *   P2HOT_AIR_CONST   index into `constants` (any 64-bit word, reduced as p2hot_stark_term.coeff is)
+ *   P2HOT_AIR_TEMP    slot < num_temps
+ * Ops: ADD / SUB / MUL  temp[dst] = a op b;  CONSTRAINT, CONSTRAINT_TRANSITION, CONSTRAINT_FIRST_ROW, CONSTRAINT_LAST_ROW consume
+ * `a` (dst and b are ignored): the four methods of ConstraintConsumer (constraint_consumer.rs:62-85), in program order,
+ * acc_j = acc_j alpha_j + c, with c first multiplied by z_last = x - w_n^-1 / L_first(x) / L_last(x) in the three filtered ones.
+ * Checked before anything is enqueued.  P2HOT_EINVAL: an unknown operand kind; a LOCAL / NEXT column beyond the trace's width; a
+ * public, constant, temp or dst index beyond its count; a temp read before any instruction wrote it; null arrays with a nonzero
+ * count; num_publics > 0 with null public_inputs; a constraint whose degree exceeds quotient_degree_factor + 1, the degree counted
+ * in units of the trace's (LOCAL, NEXT 1; PUBLIC, CONST 0; ADD, SUB the larger; MUL the sum; the first-row and last-row filters
+ * add 1, z_last does not).  P2HOT_EUNSUPPORTED: an unknown op; num_temps above p2hot_air_max_temps().  A program of num_insns == 0
+ * is valid: no constraints. */
+#define P2HOT_AIR_LOCAL 0u
+#define P2HOT_AIR_NEXT 1u
+#define P2HOT_AIR_PUBLIC 2u
+#define P2HOT_AIR_CONST 3u
+#define P2HOT_AIR_TEMP 4u
+#define P2HOT_AIR_OPERAND(kind, index) (((uint32_t)(kind) << 29) | (uint32_t)(index))
+#define P2HOT_AIR_ADD 0u
+#define P2HOT_AIR_SUB 1u
+#define P2HOT_AIR_MUL 2u
+#define P2HOT_AIR_CONSTRAINT 3u
+#define P2HOT_AIR_CONSTRAINT_TRANSITION 4u
+#define P2HOT_AIR_CONSTRAINT_FIRST_ROW 5u
+#define P2HOT_AIR_CONSTRAINT_LAST_ROW 6u
+typedef struct p2hot_air_insn { uint32_t op, dst, a, b; } p2hot_air_insn;
+typedef struct p2hot_air_program { const p2hot_air_insn *insns; const uint64_t *constants;
+                                   uint32_t num_insns, num_constants, num_temps, num_publics; } p2hot_air_program;
+/* the most temp slots a program may use: the interpreter keeps them in LDS, 8 bytes per slot and lane, 64 KiB per workgroup of 256 */
+unsigned p2hot_air_max_temps(void);
+/* ConstraintConsumer::accumulators() after Stark::eval_packed_generic alone, at every point of the quotient coset:
+ * accs_out HOST [num_challenges][n << qbits], natural order -- exactly what p2hot_stark_quotient_polys takes as constraint_accs.
+ * trace, constraint_degree, alphas and num_challenges as there (the same degrees, qbits <= rate_bits, no KeccakHash commitment). */
+int p2hot_stark_constraint_accs(p2hot_ctx *ctx, const p2hot_batch *trace, const p2hot_air_program *program,
+                                const uint64_t *public_inputs, unsigned constraint_degree, const uint64_t *alphas,
+                                unsigned num_challenges, uint64_t *accs_out);
+/* p2hot_stark_quotient_polys with the STARK's constraints as a program instead of host accumulators: the interpreter writes the
+ * accumulators into the device buffer the lookup / CTL kernel reads, so they never cross to the host.  Every rule of
+ * p2hot_stark_quotient_polys holds; an empty program is its constraint_accs = NULL. */
+int p2hot_stark_quotient_polys_air(p2hot_ctx *ctx, const p2hot_batch *trace, const p2hot_batch *aux, const p2hot_stark_tables *tables,
+                                   const p2hot_stark_lookup *lookups, unsigned num_lookups, const uint64_t *lookup_challenges,
+                                   const p2hot_stark_ctl_z *ctl_zs, unsigned num_ctl_zs, const unsigned *ctl_num_helpers,
+                                   unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges,
+                                   const p2hot_air_program *program, const uint64_t *public_inputs,
+                                   uint64_t *values_out, p2hot_cols **chunks_out);
 
 /* ================================================================ batch FRI: polynomials of several degrees, one tree, one proof
  * plonky2/src/batch_fri/{oracle,prover}.rs over hash/batch_merkle_tree.rs.  Poseidon configuration, one GPU, blinding = false: a

@@ -293,6 +293,45 @@ pub struct P2hotStarkTables {
     pub num_looking: u32,
 }
 
+/// p2hot_air_insn: one instruction of a constraint program; `a` and `b` are operands (`air_operand`), `dst` a temp slot
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct P2hotAirInsn {
+    pub op: u32,
+    pub dst: u32,
+    pub a: u32,
+    pub b: u32,
+}
+
+/// p2hot_air_program: a STARK's own constraints (`Stark::eval_packed_generic`) as a straight-line program over the evaluation frame
+#[repr(C)]
+pub struct P2hotAirProgram {
+    pub insns: *const P2hotAirInsn,
+    pub constants: *const u64,
+    pub num_insns: u32,
+    pub num_constants: u32,
+    pub num_temps: u32,
+    pub num_publics: u32,
+}
+
+pub const P2HOT_AIR_LOCAL: u32 = 0;
+pub const P2HOT_AIR_NEXT: u32 = 1;
+pub const P2HOT_AIR_PUBLIC: u32 = 2;
+pub const P2HOT_AIR_CONST: u32 = 3;
+pub const P2HOT_AIR_TEMP: u32 = 4;
+pub const P2HOT_AIR_ADD: u32 = 0;
+pub const P2HOT_AIR_SUB: u32 = 1;
+pub const P2HOT_AIR_MUL: u32 = 2;
+pub const P2HOT_AIR_CONSTRAINT: u32 = 3;
+pub const P2HOT_AIR_CONSTRAINT_TRANSITION: u32 = 4;
+pub const P2HOT_AIR_CONSTRAINT_FIRST_ROW: u32 = 5;
+pub const P2HOT_AIR_CONSTRAINT_LAST_ROW: u32 = 6;
+
+/// P2HOT_AIR_OPERAND: the kind in the top 3 bits, the index in the low 29
+pub const fn air_operand(kind: u32, index: u32) -> u32 {
+    (kind << 29) | index
+}
+
 /// p2hot_allgather_fn
 pub type P2hotAllgatherFn = Option<
     unsafe extern "C" fn(user: *mut c_void, d_base: *mut c_void, offsets: *const usize, world: c_int, bytes: usize, hip_stream: *mut c_void) -> c_int,
@@ -493,6 +532,17 @@ extern "C" {
         num_lookups: c_uint, lookup_challenges: *const u64, ctl_zs: *const P2hotStarkCtlZ, num_ctl_zs: c_uint, ctl_num_helpers: *const c_uint,
         constraint_degree: c_uint, alphas: *const u64, num_challenges: c_uint, constraint_accs: *const *const u64, values_out: *mut u64,
         chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
+    pub fn p2hot_air_max_temps() -> c_uint;
+    pub fn p2hot_stark_constraint_accs(
+        ctx: *mut P2hotCtx, trace: *const P2hotBatch, program: *const P2hotAirProgram, public_inputs: *const u64, constraint_degree: c_uint,
+        alphas: *const u64, num_challenges: c_uint, accs_out: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_stark_quotient_polys_air(
+        ctx: *mut P2hotCtx, trace: *const P2hotBatch, aux: *const P2hotBatch, tables: *const P2hotStarkTables, lookups: *const P2hotStarkLookup,
+        num_lookups: c_uint, lookup_challenges: *const u64, ctl_zs: *const P2hotStarkCtlZ, num_ctl_zs: c_uint, ctl_num_helpers: *const c_uint,
+        constraint_degree: c_uint, alphas: *const u64, num_challenges: c_uint, program: *const P2hotAirProgram, public_inputs: *const u64,
+        values_out: *mut u64, chunks_out: *mut *mut P2hotCols,
     ) -> c_int;
     pub fn p2hot_gate_sums(
         ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize, gates: *const P2hotGateSet,

@@ -90,6 +90,15 @@ class StarkTables(C.Structure):  # p2hot_stark_tables
                [(name, C.c_uint32) for name in ("num_terms", "num_columns", "num_products", "num_constants", "num_filters", "num_looking")]
 
 
+class AirInsn(C.Structure):  # p2hot_air_insn
+    _fields_ = [(name, C.c_uint32) for name in ("op", "dst", "a", "b")]
+
+
+class AirProgram(C.Structure):  # p2hot_air_program
+    _fields_ = [("insns", C.POINTER(AirInsn)), ("constants", C.POINTER(u64))] + \
+               [(name, C.c_uint32) for name in ("num_insns", "num_constants", "num_temps", "num_publics")]
+
+
 # p2hot_allgather_fn: (user, d_base, offsets, world, bytes, hip_stream) -> int
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.POINTER(sz), C.c_int, sz, vp)
 
@@ -183,6 +192,9 @@ SIGNATURES = {
     "p2hot_stark_lookup_polys": (i, [vp, vp, vp, vp, u, vp, u, u, vp, C.POINTER(vp)]),
     "p2hot_stark_ctl_polys": (i, [vp, vp, vp, vp, u, u, vp, C.POINTER(vp), vp]),
     "p2hot_stark_quotient_polys": (i, [vp, vp, vp, vp, vp, u, vp, vp, u, vp, u, vp, u, C.POINTER(vp), vp, C.POINTER(vp)]),
+    "p2hot_air_max_temps": (u, []),
+    "p2hot_stark_constraint_accs": (i, [vp, vp, vp, vp, u, vp, u, vp]),
+    "p2hot_stark_quotient_polys_air": (i, [vp, vp, vp, vp, vp, u, vp, vp, u, vp, u, vp, u, vp, vp, vp, C.POINTER(vp)]),
     "p2hot_batch_merkle_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, u, vp, vp]),
     "p2hot_batch_merkle_rows_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, vp, sz, vp]),
     "p2hot_batch_merkle_paths_dev": (i, [vp, vp, C.POINTER(u), sz, u, vp, sz, vp]),

@@ -6,6 +6,8 @@
 //   cross_table_lookup_data / partial_sums            cross_table_lookup.rs:270-414                     p2hot_stark_ctl_polys
 //   compute_quotient_polys, the arguments' terms      prover.rs:488-671, lookup.rs:804-863,
 //                                                     cross_table_lookup.rs:558-629                     p2hot_stark_quotient_polys
+//   ... with Stark::eval_packed_generic as a constraint program (host_air.hpp, air.hpp)                 p2hot_stark_quotient_polys_air
+//   the program's consumer accumulators alone                                                           p2hot_stark_constraint_accs
 #pragma once
 
 namespace {
@@ -236,13 +238,47 @@ extern "C" int p2hot_stark_ctl_polys(p2hot_ctx *ctx, const p2hot_cols *trace, co
     return stark_aux_polys(ctx, "stark_ctl_polys", trace, pl, out_host, out_cols, zs_first, pl.num_ctl_helpers, num_zs);
 }
 
-extern "C" int p2hot_stark_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *trace, const p2hot_batch *aux, const p2hot_stark_tables *tables,
-                                          const p2hot_stark_lookup *lookups, unsigned num_lookups, const uint64_t *lookup_challenges,
-                                          const p2hot_stark_ctl_z *ctl_zs, unsigned num_ctl_zs, const unsigned *ctl_num_helpers,
-                                          unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges,
-                                          const uint64_t *const *constraint_accs, uint64_t *values_out, p2hot_cols **chunks_out) {
-    P2_ENTER(ctx);
-    const char *what = "stark_quotient_polys";
+// ZeroPolyOnCoset::new(degree_bits, qbits) (field/src/zero_poly_coset.rs:21-34) on the host: out[2 << qbits], the evaluations
+// and then their inverses
+static int stark_zero_poly_on_coset(p2hot_ctx *ctx, const char *what, unsigned degree_bits, unsigned qbits, u64 *out) {
+    const size_t n = (size_t)1 << degree_bits, rate = (size_t)1 << qbits;
+    const u64 g_pow_n = gl::pow(gl::COSET_SHIFT, n), v = gl::root_of_unity(qbits);
+    for (size_t j = 0; j < rate; ++j) {
+        const u64 e = gl::canon(gl::sub(gl::mul(g_pow_n, gl::pow(v, j)), 1));
+        if (e == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: Z_H vanishes on the coset", what);
+        out[j] = e;
+        out[rate + j] = gl::inv(e);
+    }
+    return P2HOT_OK;
+}
+
+// 1 / (n (x - 1)) for every point of the quotient coset: the table p2hot_quotient_polys keeps (sizes only)
+static int stark_inv_nx1_table(p2hot_ctx *ctx, const char *what, unsigned degree_bits, unsigned qbits, const u64 **out) {
+    const unsigned log_nq = degree_bits + qbits;
+    const size_t n = (size_t)1 << degree_bits, m = n << qbits;
+    const auto inv_key = std::make_tuple(100, log_nq, qbits);
+    auto inv_it = ctx->twid_cache.find(inv_key);
+    if (inv_it == ctx->twid_cache.end()) {
+        u64 *t = nullptr;
+        P2_HIP(ctx, hipMalloc((void **)&t, m * 8));
+        P2HOT_LAUNCH(plonk::quot_inv_kernel, dim3(cdiv(m, 256)), dim3(256), 0, ctx->stream, t, log_nq, (u64)n % gl::P, ctx->fwd);
+        if (hipGetLastError() != hipSuccess) {
+            (void)hipFree(t);
+            P2_FAIL(ctx, P2HOT_EHIP, "%s: the L_first denominator table could not be launched", what);
+        }
+        inv_it = ctx->twid_cache.emplace(inv_key, t).first;
+    }
+    *out = inv_it->second;
+    return P2HOT_OK;
+}
+
+// p2hot_stark_quotient_polys and p2hot_stark_quotient_polys_air: the STARK's own constraints as the caller's host accumulators
+// (constraint_accs, or null) or, with use_air, as a program the interpreter turns into the same [nc][Nq] device buffer
+static int stark_quotient_impl(p2hot_ctx *ctx, const char *what, const p2hot_batch *trace, const p2hot_batch *aux, const p2hot_stark_tables *tables,
+                               const p2hot_stark_lookup *lookups, unsigned num_lookups, const uint64_t *lookup_challenges,
+                               const p2hot_stark_ctl_z *ctl_zs, unsigned num_ctl_zs, const unsigned *ctl_num_helpers, unsigned constraint_degree,
+                               const uint64_t *alphas, unsigned num_challenges, const uint64_t *const *constraint_accs, bool use_air,
+                               const p2hot_air_program *program, const uint64_t *public_inputs, uint64_t *values_out, p2hot_cols **chunks_out) {
     if (chunks_out) *chunks_out = nullptr;
     if (!trace || !alphas) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null argument", what);
     if (!chunks_out && !values_out) P2_FAIL(ctx, P2HOT_EINVAL, "%s: nothing asked for", what);
@@ -266,53 +302,43 @@ extern "C" int p2hot_stark_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *tra
         if (!constraint_accs[c]) P2_FAIL(ctx, P2HOT_EINVAL, "%s: constraint_accs[%u] is null", what, c);
     const unsigned degree_bits = trace->log_n, log_nq = degree_bits + qbits, K = pl.K;
     P2_TRY(check_log(ctx, log_nq, what));
+    AirPlan airp;
+    if (use_air) P2_TRY(air_plan(ctx, what, program, public_inputs, trace->W, alphas, nc, qdf + 1, &airp));
+    const bool run_air = use_air && !airp.empty(), have_accs = constraint_accs || run_air;
     const size_t n = (size_t)1 << degree_bits, m = n << qbits, rate = (size_t)1 << qbits;
-    // ZeroPolyOnCoset::new(degree_bits, qbits) (field/src/zero_poly_coset.rs:21-34) and the alpha powers, on the host
+    // ZeroPolyOnCoset::new(degree_bits, qbits) and the alpha powers, on the host
     const size_t n_small = 2 * rate + (size_t)nc * (K + 1);
     std::vector<u64> small(n_small);
-    const u64 g_pow_n = gl::pow(gl::COSET_SHIFT, n), v = gl::root_of_unity(qbits);
-    for (size_t j = 0; j < rate; ++j) {
-        const u64 e = gl::canon(gl::sub(gl::mul(g_pow_n, gl::pow(v, j)), 1));
-        if (e == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: Z_H vanishes on the coset", what);
-        small[j] = e;
-        small[rate + j] = gl::inv(e);
-    }
+    P2_TRY(stark_zero_poly_on_coset(ctx, what, degree_bits, qbits, small.data()));
     for (unsigned a = 0; a < nc; ++a) {  // term t carries alpha^(K-1-t); the caller's accumulator alpha^K
         u64 *ap = small.data() + 2 * rate + (size_t)a * (K + 1), pw = 1;
         for (unsigned t = 0; t < K; ++t, pw = gl::mul(pw, alphas[a])) ap[K - 1 - t] = gl::canon(pw);
         ap[K] = gl::canon(pw);
     }
-    PoolBuf d_work(ctx), d_small(ctx), d_desc(ctx), d_acc(ctx);
+    PoolBuf d_work(ctx), d_small(ctx), d_desc(ctx), d_acc(ctx), d_air(ctx);
     stark::TermArgs q{};
+    air::Args qa{};
     P2_TRY(pool_alloc(ctx, (size_t)nc * m * 8 + 8, &d_work.p));
     P2_TRY(pool_alloc(ctx, n_small * 8, &d_small.p));
     P2_TRY(stark_blob_alloc(ctx, pl, d_desc, &q.t));
-    if (constraint_accs) P2_TRY(pool_alloc(ctx, (size_t)nc * m * 8, &d_acc.p));
-    // 1 / (n (x - 1)) for every point of the quotient coset: the table p2hot_quotient_polys keeps (sizes only)
-    const auto inv_key = std::make_tuple(100, log_nq, qbits);
-    auto inv_it = ctx->twid_cache.find(inv_key);
-    if (inv_it == ctx->twid_cache.end()) {
-        u64 *t = nullptr;
-        P2_HIP(ctx, hipMalloc((void **)&t, m * 8));
-        P2HOT_LAUNCH(plonk::quot_inv_kernel, dim3(cdiv(m, 256)), dim3(256), 0, ctx->stream, t, log_nq, (u64)n % gl::P, ctx->fwd);
-        if (hipGetLastError() != hipSuccess) {
-            (void)hipFree(t);
-            P2_FAIL(ctx, P2HOT_EHIP, "%s: the L_first denominator table could not be launched", what);
-        }
-        inv_it = ctx->twid_cache.emplace(inv_key, t).first;
-    }
+    if (have_accs) P2_TRY(pool_alloc(ctx, (size_t)nc * m * 8, &d_acc.p));
+    if (run_air) P2_TRY(air_blob_alloc(ctx, airp, d_air, &qa));
+    P2_TRY(stark_inv_nx1_table(ctx, what, degree_bits, qbits, &q.inv_nx1));
     q.trace = trace->d_lde, q.trace_stride = trace->col_stride_lde();
     q.aux = aux ? aux->d_lde : nullptr, q.aux_stride = aux ? aux->col_stride_lde() : 0;
-    q.zh = d_small.u(), q.apow = d_small.u() + 2 * rate, q.inv_nx1 = inv_it->second;
-    q.accs = constraint_accs ? d_acc.u() : nullptr, q.out = d_work.u();
+    q.zh = d_small.u(), q.apow = d_small.u() + 2 * rate;
+    q.accs = have_accs ? d_acc.u() : nullptr, q.out = d_work.u();
     q.num_z = (unsigned)pl.zs.size(), q.K = K, q.chunk = pl.chunk, q.log_nq = log_nq, q.qbits = qbits;
     q.last = gl::inv(gl::root_of_unity(degree_bits));  // prover.rs:538
     q.roots = ctx->fwd;
+    qa.trace = q.trace, qa.stride = q.trace_stride, qa.zh = q.zh, qa.inv_nx1 = q.inv_nx1, qa.out = d_acc.u();
+    qa.log_nq = log_nq, qa.qbits = qbits, qa.last = q.last, qa.roots = ctx->fwd;
     auto body = [&]() -> int {
         P2_HIP(ctx, hipMemcpyAsync(d_small.p, small.data(), small.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         P2_HIP(ctx, hipMemcpyAsync(d_desc.p, pl.blob.data(), pl.blob.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         for (unsigned c = 0; c < nc && constraint_accs; ++c)
             P2_HIP(ctx, hipMemcpyAsync(d_acc.u() + (size_t)c * m, constraint_accs[c], m * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (run_air) P2_TRY(air_enqueue(ctx, airp, d_air, qa, nc));
         ProfScope prof(ctx, "stark_aux_terms");
         const dim3 grid(cdiv(m, 256)), block(256);
         switch (nc) {
@@ -328,4 +354,68 @@ extern "C" int p2hot_stark_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *tra
     int rc = body();
     if (rc != P2HOT_OK || !chunks_out) return sync_checked(ctx, rc, what);
     return quotient_chunks_core(ctx, d_work, nc, degree_bits, qbits, qdf, what, chunks_out);
+}
+
+extern "C" int p2hot_stark_quotient_polys(p2hot_ctx *ctx, const p2hot_batch *trace, const p2hot_batch *aux, const p2hot_stark_tables *tables,
+                                          const p2hot_stark_lookup *lookups, unsigned num_lookups, const uint64_t *lookup_challenges,
+                                          const p2hot_stark_ctl_z *ctl_zs, unsigned num_ctl_zs, const unsigned *ctl_num_helpers,
+                                          unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges,
+                                          const uint64_t *const *constraint_accs, uint64_t *values_out, p2hot_cols **chunks_out) {
+    P2_ENTER(ctx);
+    return stark_quotient_impl(ctx, "stark_quotient_polys", trace, aux, tables, lookups, num_lookups, lookup_challenges, ctl_zs, num_ctl_zs,
+                               ctl_num_helpers, constraint_degree, alphas, num_challenges, constraint_accs, false, nullptr, nullptr, values_out, chunks_out);
+}
+
+extern "C" int p2hot_stark_quotient_polys_air(p2hot_ctx *ctx, const p2hot_batch *trace, const p2hot_batch *aux, const p2hot_stark_tables *tables,
+                                              const p2hot_stark_lookup *lookups, unsigned num_lookups, const uint64_t *lookup_challenges,
+                                              const p2hot_stark_ctl_z *ctl_zs, unsigned num_ctl_zs, const unsigned *ctl_num_helpers,
+                                              unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges,
+                                              const p2hot_air_program *program, const uint64_t *public_inputs, uint64_t *values_out,
+                                              p2hot_cols **chunks_out) {
+    P2_ENTER(ctx);
+    return stark_quotient_impl(ctx, "stark_quotient_polys_air", trace, aux, tables, lookups, num_lookups, lookup_challenges, ctl_zs, num_ctl_zs,
+                               ctl_num_helpers, constraint_degree, alphas, num_challenges, nullptr, true, program, public_inputs, values_out, chunks_out);
+}
+
+extern "C" int p2hot_stark_constraint_accs(p2hot_ctx *ctx, const p2hot_batch *trace, const p2hot_air_program *program, const uint64_t *public_inputs,
+                                           unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges, uint64_t *accs_out) {
+    P2_ENTER(ctx);
+    const char *what = "stark_constraint_accs";
+    if (!trace || !alphas || !accs_out) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null argument", what);
+    if (trace->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: the commitment belongs to another context", what);
+    if (trace->hash_n) P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: KeccakHash commitments are not supported", what);
+    const unsigned nc = num_challenges;
+    if (nc == 0 || nc > 4) P2_FAIL(ctx, P2HOT_EINVAL, "%s: %u challenges (1..4)", what, nc);
+    // the degrees p2hot_stark_quotient_polys takes: 1 is rejected there with the descriptors, 0 is qdf 1
+    if (constraint_degree == 1) P2_FAIL(ctx, P2HOT_EINVAL, "%s: constraint_degree 1 (chunks of constraint_degree - 1 = 0 columns)", what);
+    const unsigned qdf = constraint_degree >= 2 ? constraint_degree - 1 : 1;
+    unsigned qbits = 0;
+    while ((1u << qbits) < qdf) ++qbits;
+    if (qbits > trace->rate_bits) P2_FAIL(ctx, P2HOT_EINVAL, "%s: quotient degree 2^%u above the rate 2^%u (prover.rs:517-520)", what, qbits, trace->rate_bits);
+    const unsigned degree_bits = trace->log_n, log_nq = degree_bits + qbits;
+    P2_TRY(check_log(ctx, log_nq, what));
+    AirPlan airp;
+    P2_TRY(air_plan(ctx, what, program, public_inputs, trace->W, alphas, nc, qdf + 1, &airp));
+    const size_t m = (size_t)1 << log_nq, rate = (size_t)1 << qbits;
+    if (airp.empty()) {  // no constraints: the consumer's accumulators stay zero
+        std::fill(accs_out, accs_out + (size_t)nc * m, (uint64_t)0);
+        return P2HOT_OK;
+    }
+    std::vector<u64> zh(2 * rate);
+    P2_TRY(stark_zero_poly_on_coset(ctx, what, degree_bits, qbits, zh.data()));
+    PoolBuf d_acc(ctx), d_zh(ctx), d_air(ctx);
+    air::Args qa{};
+    P2_TRY(pool_alloc(ctx, (size_t)nc * m * 8, &d_acc.p));
+    P2_TRY(pool_alloc(ctx, zh.size() * 8, &d_zh.p));
+    P2_TRY(air_blob_alloc(ctx, airp, d_air, &qa));
+    P2_TRY(stark_inv_nx1_table(ctx, what, degree_bits, qbits, &qa.inv_nx1));
+    qa.trace = trace->d_lde, qa.stride = trace->col_stride_lde(), qa.zh = d_zh.u(), qa.out = d_acc.u();
+    qa.log_nq = log_nq, qa.qbits = qbits, qa.last = gl::inv(gl::root_of_unity(degree_bits)), qa.roots = ctx->fwd;
+    auto body = [&]() -> int {
+        P2_HIP(ctx, hipMemcpyAsync(d_zh.p, zh.data(), zh.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        P2_TRY(air_enqueue(ctx, airp, d_air, qa, nc));
+        P2_HIP(ctx, hipMemcpyAsync(accs_out, d_acc.p, (size_t)nc * m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return P2HOT_OK;
+    };
+    return sync_checked(ctx, body(), what);
 }

@@ -1,5 +1,5 @@
 // p2hot.hip -- context, pass planning and the C ABI of libp2hot (see include/p2hot.h).
-// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / stark.hpp / gates.hpp / gates_recursion.hpp.
+// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / stark.hpp / air.hpp / gates.hpp / gates_recursion.hpp.
 #include "../../include/p2hot.h"
 
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "plonk.hpp"
 #include "lookup.hpp"
 #include "stark.hpp"
+#include "air.hpp"
 #include "gates.hpp"
 #include "gates_recursion.hpp"
 #include "merkle.hpp"
@@ -2109,6 +2110,7 @@ struct p2hot_cols {
 };
 
 #include "host_prover.hpp"
+#include "host_air.hpp"
 #include "host_stark.hpp"
 #include "host_multi.hpp"
 #include "batch_fri.hpp"
