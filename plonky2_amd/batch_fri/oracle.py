@@ -11,7 +11,7 @@ import numpy as np
 
 from .. import _lib
 from ..engine import default_engine
-from ..fri.oracle import FriBatchInfo, shape_fri_proof
+from ..fri.oracle import FriBatchInfo, fri_batch_infos, fri_params, fri_proof_buffers, shape_fri_proof
 from ..hash.merkle_tree import MerkleCap
 
 
@@ -140,32 +140,20 @@ class BatchFriOracle:
         p2hot_batch_prove_openings call.  Returns the FriProof-shaped dict of fri.oracle.prove_openings; an initial leaf is
         values(x_index) flattened, its siblings open_batch(x_index)."""
         eng = engine or oracles[0].engine
-        arity = [int(a) for a in reduction_arity_bits]
-        R, Q = len(arity), int(num_query_rounds)
-        ab = (C.c_uint * max(R, 1))(*arity)
-        fp = _lib.FriParams(rate_bits, cap_height, proof_of_work_bits, Q, ab, R, 0, max_num_query_steps or 0, final_poly_coeff_len or 0)
+        fp, arity = fri_params(rate_bits, cap_height, reduction_arity_bits, proof_of_work_bits, num_query_rounds, max_num_query_steps,
+                               final_poly_coeff_len)
+        Q = int(num_query_rounds)
         keep = []  # arrays referenced by the structs
         insts = (_lib.FriInstance * max(len(instances), 1))()
         for i, inst in enumerate(instances):
-            infos = (_lib.FriBatchInfo * max(len(inst.batches), 1))()
-            for k, b in enumerate(inst.batches):
-                oi = (C.c_uint32 * max(len(b.polynomials), 1))(*[o for o, _ in b.polynomials])
-                pi = (C.c_uint32 * max(len(b.polynomials), 1))(*[p for _, p in b.polynomials])
-                keep += [oi, pi]
-                infos[k].point[0], infos[k].point[1] = b.point
-                infos[k].oracle_index, infos[k].poly_index, infos[k].n_polys = oi, pi, len(b.polynomials)
+            infos = fri_batch_infos(inst.batches, keep)
             keep.append(infos)
             insts[i].batches, insts[i].n_batches = infos, len(inst.batches)
         db = (C.c_uint * max(len(degree_bits), 1))(*[int(d) for d in degree_bits])
         handles = (C.c_void_p * max(len(oracles), 1))(*[o._h for o in oracles])
         lay = _lib.FriProofLayout()
         rc = eng.lib.p2hot_batch_fri_proof_sizes(handles, len(oracles), C.byref(fp), C.byref(lay))
-        bufs = {k: np.zeros(max(1, getattr(lay, k + "_words") if rc == _lib.OK else 1), dtype=np.uint64)
-                for k in ("caps", "final_poly", "initial_leaves", "initial_paths", "step_evals", "step_paths")}
-        qidx = np.zeros(max(1, Q), dtype=np.uint64)
-        proof = _lib.FriProof(bufs["caps"].ctypes.data, bufs["final_poly"].ctypes.data, 0, qidx.ctypes.data,
-                              bufs["initial_leaves"].ctypes.data, bufs["initial_paths"].ctypes.data,
-                              bufs["step_evals"].ctypes.data, bufs["step_paths"].ctypes.data)
+        bufs, qidx, proof = fri_proof_buffers(lay if rc == _lib.OK else None, Q)
         # (inconsistent parameters are reported by the call itself, with the argument named)
         eng.check(eng.lib.p2hot_batch_prove_openings(eng.ctx, db, insts, len(instances), handles, len(oracles), challenger._h,
                                                      C.byref(fp), C.byref(proof)))

@@ -176,7 +176,10 @@ extern "C" int p2hot_batch_fri_commit_dev(p2hot_ctx *ctx, const uint64_t *const 
         if (!d_coeffs_planar[j]) P2_FAIL(ctx, P2HOT_EINVAL, "batch_fri_commit: the coefficients of instance %zu are null", j);
     const BatchJoin join{d_coeffs_planar + 1, log_n + 1, n_instances - 1};
     return fri_commit_core(ctx, nullptr, d_coeffs_planar[0], log_n[0], rate_bits, cap_height, arity_bits, n_rounds, 0, 0, challenger,
-                           d_leaves_out, true, digests_out, digests_on_device != 0, caps_out, betas_out, final_out, false, &join);
+                           FriCommitOut{.leaves_out = d_leaves_out, .leaves_on_device = true, .digests_out = digests_out,
+                                        .digests_on_device = digests_on_device != 0, .caps_out = caps_out, .betas_out = betas_out,
+                                        .final_out = final_out},
+                           &join);
 }
 
 // ------------------------------------------------------------------ BatchFriOracle, host pointers
@@ -381,11 +384,8 @@ extern "C" int p2hot_batch_prove_openings(p2hot_ctx *ctx, const unsigned *degree
     if (fp->max_num_query_steps || fp->final_poly_coeff_len)
         P2_FAIL(ctx, P2HOT_EINVAL, "%s: max_num_query_steps / final_poly_coeff_len do not exist on the batch path (batch_fri/prover.rs:88-97)", what);
     P2_TRY(batch_join_check(ctx, degree_bits, n_instances, fp->reduction_arity_bits, fp->n_reduction_rounds, what));
-    const unsigned log_n = degree_bits[0];
-    P2_TRY(fri_check_params(ctx, fp, log_n));
-    const unsigned rate_bits = fp->rate_bits, cap_height = fp->cap_height, log_N = log_n + rate_bits, n_rounds = fp->n_reduction_rounds;
-    if (n_rounds > 32) P2_FAIL(ctx, P2HOT_EINVAL, "%s: more than 32 reduction rounds", what);
-    if (fp->proof_of_work_bits > 64) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof_of_work_bits > 64", what);
+    const unsigned rate_bits = fp->rate_bits, cap_height = fp->cap_height, log_N = degree_bits[0] + rate_bits;
+    std::vector<size_t> leaf_widths;
     for (size_t o = 0; o < n_oracles; ++o) {
         const p2hot_batch_oracle *B = oracles[o];
         if (!B || B->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: oracle %zu is null or belongs to another context", what, o);
@@ -394,13 +394,13 @@ extern "C" int p2hot_batch_prove_openings(p2hot_ctx *ctx, const unsigned *degree
         if (B->log_heights[0] != log_N)
             P2_FAIL(ctx, P2HOT_EINVAL, "%s: the tallest group of oracle %zu has 2^%u rows, not 2^(degree_bits[0] + rate_bits) = 2^%u", what, o,
                     B->log_heights[0], log_N);
+        leaf_widths.push_back(B->W);
     }
     // the polynomial table of every instance (FriInstanceInfo.batches): device pointers in batch order
-    std::vector<std::vector<const u64 *>> ptrs(n_instances);
-    std::vector<std::vector<size_t>> offsets(n_instances, std::vector<size_t>(1, 0));
-    std::vector<std::vector<u64>> points(n_instances);
-    size_t table_words = 0, plane_words = 0;
+    std::vector<OpeningInstance> tables(n_instances);
     for (size_t i = 0; i < n_instances; ++i) {
+        OpeningInstance &in = tables[i];
+        in.log_n = degree_bits[i];
         if (instances[i].n_batches && !instances[i].batches) P2_FAIL(ctx, P2HOT_EINVAL, "%s: instance %zu has null batches", what, i);
         for (size_t b = 0; b < instances[i].n_batches; ++b) {
             const p2hot_fri_batch_info &bi = instances[i].batches[b];
@@ -413,157 +413,19 @@ extern "C" int p2hot_batch_prove_openings(p2hot_ctx *ctx, const unsigned *degree
                 if (oracles[oi]->log_n[pi] != degree_bits[i])
                     P2_FAIL(ctx, P2HOT_EINVAL, "%s: instance %zu opens polynomial (%zu, %zu) of degree 2^%u, not 2^degree_bits[%zu] = 2^%u "
                             "(batch_fri/oracle.rs:170)", what, i, oi, pi, oracles[oi]->log_n[pi], i, degree_bits[i]);
-                ptrs[i].push_back(oracles[oi]->d_coef + oracles[oi]->coef_off[pi]);
+                in.ptrs.push_back(oracles[oi]->d_coef + oracles[oi]->coef_off[pi]);
             }
-            offsets[i].push_back(ptrs[i].size());
-            points[i].push_back(bi.point[0]);
-            points[i].push_back(bi.point[1]);
-        }
-        table_words += ptrs[i].size();
-        plane_words += (size_t)2 << degree_bits[i];
-    }
-    const size_t n = (size_t)1 << log_n, N = n << rate_bits, Q = fp->num_query_rounds;
-    p2hot_fri_proof_layout lay;
-    {
-        std::vector<size_t> widths;
-        for (size_t o = 0; o < n_oracles; ++o) widths.push_back(oracles[o]->W);
-        if (fri_proof_layout(widths.data(), n_oracles, log_n, fp, &lay) != P2HOT_OK) P2_FAIL(ctx, P2HOT_EINVAL, "%s: inconsistent parameters", what);
-    }
-    if ((lay.caps_words && !proof->commit_phase_merkle_caps) || !proof->final_poly ||
-        (Q && ((lay.initial_leaves_words && !proof->initial_leaves) || (lay.initial_paths_words && !proof->initial_paths) ||
-               (lay.step_evals_words && !proof->step_evals) || (lay.step_paths_words && !proof->step_paths))))
-        P2_FAIL(ctx, P2HOT_EINVAL, "%s: a proof buffer is null (size them with p2hot_batch_fri_proof_sizes)", what);
-    // --- device blocks: pointer tables, one final_poly plane pair per instance, round trees (leaves + digests), query staging
-    size_t leaf_words = 0, dig_words = 0;
-    {
-        size_t m = N;
-        unsigned lm = log_N;
-        for (unsigned r = 0; r < n_rounds; ++r) {
-            const unsigned ab = fp->reduction_arity_bits[r];
-            leaf_words += 2 * m;
-            dig_words += 4 * p2hot_num_digests(lm - ab, cap_height);
-            m >>= ab;
-            lm -= ab;
+            in.offsets.push_back(in.ptrs.size());
+            in.points.push_back(bi.point[0]);
+            in.points.push_back(bi.point[1]);
         }
     }
-    const unsigned layers0 = log_N - cap_height;
-    PoolBuf d_table(ctx), d_planes(ctx), d_leaves(ctx), d_dig(ctx), d_q(ctx);
-    P2_TRY(pool_alloc(ctx, (table_words ? table_words : 1) * sizeof(u64 *), &d_table.p));
-    P2_TRY(pool_alloc(ctx, plane_words * 8, &d_planes.p));
-    P2_TRY(pool_alloc(ctx, (leaf_words ? leaf_words : 1) * 8, &d_leaves.p));
-    P2_TRY(pool_alloc(ctx, (dig_words ? dig_words : 1) * 8, &d_dig.p));
-    const size_t ch_words = (sizeof(fri::Challenger) + 7) / 8;
-    const size_t q_words = Q * (1 + n_rounds) + lay.initial_leaves_words + lay.initial_paths_words + lay.step_evals_words +
-                           lay.step_paths_words + Q + 2 + 1 + 1 + ch_words;
-    P2_TRY(pool_alloc(ctx, q_words * 8, &d_q.p));
-    u64 *d_idx = d_q.u(), *d_il = d_idx + Q * (1 + n_rounds), *d_ip = d_il + lay.initial_leaves_words,
-        *d_se = d_ip + lay.initial_paths_words, *d_sp = d_se + lay.step_evals_words, *d_rand = d_sp + lay.step_paths_words,
-        *d_alpha = d_rand + Q, *d_best = d_alpha + 2, *d_resp = d_best + 1, *d_chsave = d_resp + 1;
-    fri::ArityBits ab{};
-    for (unsigned r = 0; r < n_rounds; ++r) ab.b[r] = (unsigned char)fp->reduction_arity_bits[r];
-    size_t w_sum = 0;
-    for (size_t o = 0; o < n_oracles; ++o) w_sum += oracles[o]->W;
-    std::vector<const uint64_t *> planes(n_instances);
-    {
-        u64 *p = d_planes.u();
-        for (size_t i = 0; i < n_instances; ++i) {
-            planes[i] = p;
-            p += (size_t)2 << degree_bits[i];
-        }
-    }
-    unsigned long long best = ~0ull;
-    u64 pow_next = 0;
-    // Everything below is enqueued without waiting for the GPU, as in p2hot_prove_openings: ONE synchronisation ends the call.
-    auto head = [&]() -> int {
-        // oracle.rs:138: alpha = challenger.get_extension_challenge(), once for every instance
-        P2_TRY(challenger_step_dev(challenger, nullptr, 0, d_alpha, 2));
-        // oracle.rs:143-179: one final_poly per instance; ReducingFactor's count is zero at the start of each (reduce_polys_base and
-        // shift_poly leave it at zero), so every instance is the plain prelude with the same alpha
-        const u64 **tab = (const u64 **)d_table.p;
-        for (size_t i = 0; i < n_instances; ++i) {
-            if (!ptrs[i].empty())
-                P2_HIP(ctx, hipMemcpyAsync(tab, ptrs[i].data(), ptrs[i].size() * sizeof(u64 *), hipMemcpyHostToDevice, ctx->stream));
-            P2_TRY(final_poly_core(ctx, (const uint64_t *const *)tab, offsets[i].data(), instances[i].n_batches, points[i].data(), nullptr,
-                                   d_alpha, degree_bits[i], (uint64_t *)planes[i]));
-            tab += ptrs[i].size();
-        }
-        // batch_fri/prover.rs:53-62: the commit phase; the round trees stay on the device
-        const BatchJoin join{planes.data() + 1, degree_bits + 1, n_instances - 1};
-        P2_TRY(fri_commit_core(ctx, nullptr, planes[0], log_n, rate_bits, cap_height, fp->reduction_arity_bits, n_rounds, 0, 0, challenger,
-                               d_leaves.u(), true, d_dig.u(), true, proof->commit_phase_merkle_caps, nullptr, proof->final_poly,
-                               /*defer_sync=*/true, &join));
-        // batch_fri/prover.rs:64-69: proof of work
-        P2_HIP(ctx, hipMemcpyAsync(d_chsave, challenger->d, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, ctx->stream));
-        return pow_search_dev(ctx, challenger, fp->proof_of_work_bits, (unsigned long long *)d_best, &pow_next);
+    // batch_fri/prover.rs:186-198: per oracle (values(x) flattened, open_batch(x)); the rest is the plain opening proof with the
+    // later instances joining the commit phase (prove_openings_core)
+    const DeviceOpener on_device = [&](size_t o, const u64 *d_idx, size_t Q, u64 *d_rows, u64 *d_paths) -> int {
+        const fri::BatchTreeTable t = oracles[o]->table();
+        P2_TRY(batch_rows_launch(ctx, t, d_idx, Q, d_rows));
+        return batch_paths_launch(ctx, oracles[o]->d_dig, t, d_idx, Q, d_paths);
     };
-    auto tail = [&]() -> int {
-        P2_TRY(challenger_step_dev(challenger, d_best, 1, d_resp, 1));
-        P2_TRY(d2h(ctx, &best, d_best, 8));
-        if (Q == 0) return P2HOT_OK;
-        // batch_fri/prover.rs:160-164: x_index = rand % n per query round; :209 x_index >>= arity_bits per round
-        P2_TRY(challenger_step_dev(challenger, nullptr, 0, d_rand, Q));
-        P2HOT_LAUNCH(fri::query_indices_kernel, dim3(cdiv(Q, 256)), dim3(256), 0, ctx->stream, (const u64 *)d_rand, Q, log_N, ab, n_rounds,
-                     d_idx);
-        P2_LAUNCH_CHECK(ctx);
-        if (proof->query_indices) P2_TRY(d2h(ctx, proof->query_indices, d_idx, Q * 8));
-        // batch_fri/prover.rs:186-198: per oracle (values(x) flattened, open_batch(x)); device staging oracle-major, host query-major
-        size_t w_off = 0;
-        for (size_t o = 0; o < n_oracles; ++o) {
-            const fri::BatchTreeTable t = oracles[o]->table();
-            P2_TRY(batch_rows_launch(ctx, t, d_idx, Q, d_il + Q * w_off));
-            P2_TRY(batch_paths_launch(ctx, oracles[o]->d_dig, t, d_idx, Q, d_ip + o * Q * 4 * layers0));
-            w_off += oracles[o]->W;
-        }
-        // batch_fri/prover.rs:199-210: the steps, as in the plain query round
-        size_t ev_off = 0, pa_off = 0, lv = 0, dg = 0, m = N;
-        unsigned lm = log_N;
-        std::vector<size_t> ev_offs, pa_offs, ev_w, pa_w;
-        for (unsigned r = 0; r < n_rounds; ++r) {
-            const unsigned abr = fp->reduction_arity_bits[r];
-            const size_t roww = (size_t)2 << abr, layers = lm - abr - cap_height;
-            P2HOT_LAUNCH(fri::gather_rowmajor_kernel, dim3(cdiv(Q * roww, 256)), dim3(256), 0, ctx->stream, (const u64 *)(d_leaves.u() + lv),
-                         roww, m >> abr, (const u64 *)(d_idx + (1 + (size_t)r) * Q), Q, d_se + Q * ev_off, ctx->d_oob);
-            P2_LAUNCH_CHECK(ctx);
-            if (layers)
-                P2_TRY(p2hot_merkle_paths_dev(ctx, d_dig.u() + dg, lm - abr, cap_height, d_idx + (1 + (size_t)r) * Q, Q, d_sp + Q * pa_off));
-            ev_offs.push_back(ev_off);
-            pa_offs.push_back(pa_off);
-            ev_w.push_back(roww);
-            pa_w.push_back(4 * layers);
-            ev_off += roww;
-            pa_off += 4 * layers;
-            lv += 2 * m;
-            dg += 4 * p2hot_num_digests(lm - abr, cap_height);
-            m >>= abr;
-            lm -= abr;
-        }
-        w_off = 0;
-        for (size_t o = 0; o < n_oracles; ++o) {
-            const size_t Wb = oracles[o]->W;
-            if (Wb) P2_TRY(d2h_2d(ctx, proof->initial_leaves + w_off, w_sum * 8, d_il + Q * w_off, Wb * 8, Wb * 8, Q));
-            if (layers0)
-                P2_TRY(d2h_2d(ctx, proof->initial_paths + o * 4 * layers0, n_oracles * 4 * layers0 * 8, d_ip + o * Q * 4 * layers0,
-                              4 * layers0 * 8, 4 * layers0 * 8, Q));
-            w_off += Wb;
-        }
-        for (unsigned r = 0; r < n_rounds; ++r) {
-            P2_TRY(d2h_2d(ctx, proof->step_evals + ev_offs[r], ev_off * 8, d_se + Q * ev_offs[r], ev_w[r] * 8, ev_w[r] * 8, Q));
-            if (pa_w[r])
-                P2_TRY(d2h_2d(ctx, proof->step_paths + pa_offs[r], pa_off * 8, d_sp + Q * pa_offs[r], pa_w[r] * 8, pa_w[r] * 8, Q));
-        }
-        return P2HOT_OK;
-    };
-    int rc = head();
-    if (rc == P2HOT_OK) rc = tail();
-    rc = sync_checked(ctx, rc, what);
-    if (rc == P2HOT_OK && best == ~0ull) {  // no witness in the range searched on the device: see prove_openings_core
-        auto fallback = [&]() -> int {
-            P2_HIP(ctx, hipMemcpyAsync(challenger->d, d_chsave, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, ctx->stream));
-            P2_TRY(pow_continue_host(ctx, challenger, fp->proof_of_work_bits, (unsigned long long *)d_best, pow_next, &best));
-            return tail();
-        };
-        rc = sync_checked(ctx, fallback(), what);
-    }
-    if (rc == P2HOT_OK) proof->pow_witness = best;
-    return rc;
+    return prove_openings_core(ctx, what, tables, leaf_widths, &on_device, nullptr, challenger, fp, proof);
 }

@@ -1089,6 +1089,6 @@ extern "C" int p2hot_group_prove_openings(p2hot_group *g, const p2hot_fri_batch_
             }
             return P2HOT_OK;
         };
-        return prove_openings_core(ctx, batches, n_batches, views, log_n, challenger, fp, proof, &opener);
+        return prove_openings_views(ctx, batches, n_batches, views, log_n, challenger, fp, proof, &opener);
     }
 }

@@ -826,7 +826,14 @@ struct OracleView {
     size_t col_lde() const { return lde_stride ? lde_stride : N; }
     size_t col_coef(unsigned log_n) const { return coef_stride ? coef_stride : ((size_t)1 << log_n); }
 };
-// fills proof->initial_leaves / initial_paths (query-major layout) for the Q host-resident query indices
+static OracleView view_of(const p2hot_batch *B) {
+    return OracleView{B->d_coef, B->d_lde, B->d_dig, B->W, B->N, B->S, B->lde_stride, B->coef_stride};
+}
+// How prove_openings_core opens the initial trees; exactly one of the two is given.
+// DeviceOpener: enqueues, for oracle o and the Q query indices at d_idx, the rows [Q][leaf width] and the paths [Q][layers][4]
+typedef std::function<int(size_t o, const u64 *d_idx, size_t Q, u64 *d_rows, u64 *d_paths)> DeviceOpener;
+// InitialOpener: fills proof->initial_leaves / initial_paths (query-major layout) for the Q host-resident query indices, after
+// the synchronisation that ends the device work
 typedef std::function<int(const u64 *idx, size_t Q, u64 *leaves_out, u64 *paths_out)> InitialOpener;
 
 // OpeningSet::new for oracles given as views: a device table of pointers to every polynomial in order, one
@@ -845,7 +852,7 @@ extern "C" int p2hot_eval_openings(p2hot_ctx *ctx, const p2hot_batch *const *bat
         if (!B || B->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "oracle %zu is null or belongs to another context", b);
         if (B->log_n != batches[0]->log_n)
             P2_FAIL(ctx, P2HOT_EINVAL, "all oracles must have the same degree (oracle %zu: 2^%u vs 2^%u)", b, B->log_n, batches[0]->log_n);
-        views.push_back(OracleView{B->d_coef, B->d_lde, B->d_dig, B->W, B->N, B->S, B->lde_stride, B->coef_stride});
+        views.push_back(view_of(B));
     }
     return eval_openings_core(ctx, views, batches[0]->log_n, points, n_points, out);
 }
@@ -895,19 +902,11 @@ static int eval_openings_core(p2hot_ctx *ctx, const std::vector<OracleView> &vie
 }
 
 // ------------------------------------------------------------------ prove_openings + fri_proof
-static int fri_check_params(p2hot_ctx *ctx, const p2hot_fri_params *fp, unsigned log_n) {
+static int fri_check_params(p2hot_ctx *ctx, const p2hot_fri_params *fp, unsigned log_n, FriRounds *rounds) {
     if (!fp) P2_FAIL(ctx, P2HOT_EINVAL, "null fri params");
     if (fp->n_reduction_rounds && !fp->reduction_arity_bits) P2_FAIL(ctx, P2HOT_EINVAL, "null reduction_arity_bits");
     P2_TRY(check_log(ctx, log_n + fp->rate_bits, "fri"));
-    unsigned lm = log_n + fp->rate_bits, ln = log_n;
-    for (unsigned r = 0; r < fp->n_reduction_rounds; ++r) {
-        const unsigned ab = fp->reduction_arity_bits[r];
-        if (ab == 0 || ab > ln) P2_FAIL(ctx, P2HOT_EINVAL, "fri: round %u arity 2^%u does not divide the degree bound", r, ab);
-        if (lm - ab < fp->cap_height) P2_FAIL(ctx, P2HOT_EINVAL, "fri: round %u tree has fewer leaves than the cap (merkle_tree.rs:195-200)", r);
-        lm -= ab;
-        ln -= ab;
-    }
-    return P2HOT_OK;
+    return fri_rounds(ctx, "fri", log_n, fp->rate_bits, fp->cap_height, fp->reduction_arity_bits, fp->n_reduction_rounds, rounds);
 }
 
 // sizes of the flat FriProof buffers for oracles of the given widths (include/p2hot.h, p2hot_fri_proof)
@@ -917,22 +916,15 @@ static int fri_proof_layout(const size_t *widths, size_t n_oracles, unsigned log
     size_t w_sum = 0;
     for (size_t o = 0; o < n_oracles; ++o) w_sum += widths[o];
     const size_t q = fp->num_query_rounds, cap_words = (size_t)4 << fp->cap_height;
-    size_t evals = 0, paths = 0;
-    unsigned lm = log_N;
-    for (unsigned r = 0; r < fp->n_reduction_rounds; ++r) {
-        const unsigned ab = fp->reduction_arity_bits[r];
-        if (ab > lm || lm - ab < fp->cap_height) return P2HOT_EINVAL;
-        evals += (size_t)2 << ab;
-        paths += 4 * (size_t)(lm - ab - fp->cap_height);
-        lm -= ab;
-    }
-    if (lm < fp->rate_bits || log_N < fp->cap_height) return P2HOT_EINVAL;
+    FriRounds rounds;
+    P2_TRY(fri_rounds(nullptr, nullptr, log_n, fp->rate_bits, fp->cap_height, fp->reduction_arity_bits, fp->n_reduction_rounds, &rounds));
+    if (rounds.log_last < fp->rate_bits || log_N < fp->cap_height) return P2HOT_EINVAL;
     out->caps_words = fp->n_reduction_rounds * cap_words;
-    out->final_poly_words = (size_t)2 << (lm - fp->rate_bits);
+    out->final_poly_words = (size_t)2 << (rounds.log_last - fp->rate_bits);
     out->initial_leaves_words = q * w_sum;
     out->initial_paths_words = q * n_oracles * 4 * (size_t)(log_N - fp->cap_height);
-    out->step_evals_words = q * evals;
-    out->step_paths_words = q * paths;
+    out->step_evals_words = q * rounds.ev_words;
+    out->step_paths_words = q * rounds.pa_words;
     return P2HOT_OK;
 }
 
@@ -947,9 +939,9 @@ extern "C" int p2hot_fri_proof_sizes(const p2hot_batch *const *oracles, size_t n
     return fri_proof_layout(widths.data(), n_oracles, oracles[0]->log_n, fp, out);
 }
 
-static int prove_openings_core(p2hot_ctx *ctx, const p2hot_fri_batch_info *batches, size_t n_batches, const std::vector<OracleView> &views,
-                               unsigned log_n, p2hot_challenger *challenger, const p2hot_fri_params *fp, p2hot_fri_proof *proof,
-                               const InitialOpener *open_initial);
+static int prove_openings_views(p2hot_ctx *ctx, const p2hot_fri_batch_info *batches, size_t n_batches, const std::vector<OracleView> &views,
+                                unsigned log_n, p2hot_challenger *challenger, const p2hot_fri_params *fp, p2hot_fri_proof *proof,
+                                const InitialOpener *open_initial);
 
 extern "C" int p2hot_prove_openings(p2hot_ctx *ctx, const p2hot_fri_batch_info *batches, size_t n_batches,
                                     const p2hot_batch *const *oracles, size_t n_oracles, p2hot_challenger *challenger,
@@ -972,17 +964,16 @@ extern "C" int p2hot_prove_openings(p2hot_ctx *ctx, const p2hot_fri_batch_info *
         }
         if (oracles[o]->log_n != oracles[0]->log_n || (fp && (oracles[o]->rate_bits != fp->rate_bits || oracles[o]->cap_height != fp->cap_height)))
             P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: oracle %zu was committed with another degree / rate / cap height", o);
-        views.push_back(OracleView{oracles[o]->d_coef, oracles[o]->d_lde, oracles[o]->d_dig, oracles[o]->W, oracles[o]->N, oracles[o]->S,
-                                   oracles[o]->lde_stride, oracles[o]->coef_stride});
+        views.push_back(view_of(oracles[o]));
     }
-    return prove_openings_core(ctx, batches, n_batches, views, oracles[0]->log_n, challenger, fp, proof, nullptr);
+    return prove_openings_views(ctx, batches, n_batches, views, oracles[0]->log_n, challenger, fp, proof, nullptr);
 }
 
 // ------------------------------------------------------------------ M opening proofs side by side
 // A recursion-size opening proof (2^12 rows) is a chain of small launches -- about 36 dependent challenger permutations, tree
 // levels of a few hundred nodes -- that leaves the chip almost idle.  M independent proofs therefore run on up to 4 sibling
 // contexts of the same GPU (their own streams, scratch and block caches), each driven by its own host thread, so that the
-// launches of different proofs overlap on the device.  Every proof is computed by the same prove_openings_core as a single
+// launches of different proofs overlap on the device.  Every proof is computed by the same prove_openings_views as a single
 // p2hot_prove_openings call: results are identical, buffer by buffer.
 static int helper_contexts(p2hot_ctx *ctx, size_t want) {
     while (ctx->helpers.size() < want) {
@@ -1041,7 +1032,7 @@ extern "C" int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_f
                         o, j, B->hash_n);
             if (B->log_n != oracles[0]->log_n || (fp && (B->rate_bits != fp->rate_bits || B->cap_height != fp->cap_height)))
                 P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings_many: oracle %zu of proof %zu was committed with another degree / rate / cap height", o, j);
-            views[j].push_back(OracleView{B->d_coef, B->d_lde, B->d_dig, B->W, B->N, B->S, B->lde_stride, B->coef_stride});
+            views[j].push_back(view_of(B));
         }
     }
     size_t k_max = 4;  // sibling contexts: 2 and 4 measured 1.8-1.9x a single stream, 8+ no better (P2HOT_MANY_HELPERS overrides; tools/pom_trace.py)
@@ -1060,7 +1051,7 @@ extern "C" int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_f
         for (size_t j = k; j < M && rcs[k] == P2HOT_OK; j += K) {
             auto one = [&]() -> int {
                 P2_HIP(h, hipMemcpyAsync(hc->d, challengers[j]->d, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, h->stream));
-                P2_TRY(prove_openings_core(h, batches[j], n_batches[j], views[j], log_n, hc, fp, &proofs[j], nullptr));
+                P2_TRY(prove_openings_views(h, batches[j], n_batches[j], views[j], log_n, hc, fp, &proofs[j], nullptr));
                 P2_HIP(h, hipMemcpyAsync(challengers[j]->d, hc->d, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, h->stream));
                 P2_HIP(h, stream_sync(h));
                 return P2HOT_OK;
@@ -1095,78 +1086,91 @@ extern "C" int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_f
     return P2HOT_OK;
 }
 
-static int prove_openings_core(p2hot_ctx *ctx, const p2hot_fri_batch_info *batches, size_t n_batches, const std::vector<OracleView> &views,
-                               unsigned log_n, p2hot_challenger *challenger, const p2hot_fri_params *fp, p2hot_fri_proof *proof,
-                               const InitialOpener *open_initial) {
-    const size_t n_oracles = views.size();
-    if (!challenger || challenger->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: the challenger belongs to another context");
-    if (!proof || (n_batches && !batches)) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: null argument");
+// ------------------------------------------------------------------ the opening proof: one core for plain, sharded and batch FRI
+// One FRI instance (FriInstanceInfo, fri/structure.rs): the polynomials of one degree opened at each point, as device pointers in
+// batch order.  The plain and sharded paths prove one instance; batch FRI one per degree, the largest first.
+struct OpeningInstance {
+    unsigned log_n = 0;
+    std::vector<const u64 *> ptrs;
+    std::vector<size_t> offsets = std::vector<size_t>(1, 0);  // batch b opens ptrs[offsets[b], offsets[b + 1])
+    std::vector<u64> points;                                   // [n_batches][2]
+    size_t n_batches() const { return offsets.size() - 1; }
+};
+
+// the query staging block of one proof, device words
+struct QueryStaging {
+    u64 *idx;                            // [1 + n_rounds][Q]: x_index, then x_index >> arity_bits per round
+    u64 *leaves, *paths, *evals, *step_paths;  // the four query buffers of p2hot_fri_proof, oracle- / round-major
+    u64 *rand, *alpha, *best, *resp;     // [Q] | [2] | PoW witness | PoW response
+    u64 *chsave;                         // the transcript before the grind
+};
+static int query_staging_alloc(p2hot_ctx *ctx, size_t Q, unsigned n_rounds, const p2hot_fri_proof_layout &lay, PoolBuf *block, QueryStaging *s) {
+    u64 **const member[] = {&s->idx, &s->leaves, &s->paths, &s->evals, &s->step_paths, &s->rand, &s->alpha, &s->best, &s->resp, &s->chsave};
+    const size_t words[] = {Q * (1 + n_rounds), lay.initial_leaves_words, lay.initial_paths_words, lay.step_evals_words, lay.step_paths_words,
+                            Q, 2, 1, 1, (sizeof(fri::Challenger) + 7) / 8};
+    size_t total = 0;
+    for (size_t w : words) total += w;
+    P2_TRY(pool_alloc(ctx, total * 8, &block->p));
+    u64 *p = block->u();
+    for (size_t k = 0; k < sizeof words / sizeof *words; ++k) {
+        *member[k] = p;
+        p += words[k];
+    }
+    return P2HOT_OK;
+}
+
+// PolynomialBatch::prove_openings + fri_proof (fri/oracle.rs:176-237, fri/prover.rs:24-82) and their batch_fri counterparts
+// (batch_fri/oracle.rs:128-192, batch_fri/prover.rs:25-86) after the caller's own validation.  `what` starts every error text.
+// instances[0] has the largest degree and sets the proof's geometry; instances 1.. join the commit phase when the folded degree
+// reaches theirs (the caller has checked that it does: batch_join_check).  leaf_widths: words of an initial leaf, per oracle.
+static int prove_openings_core(p2hot_ctx *ctx, const char *what, const std::vector<OpeningInstance> &instances,
+                               const std::vector<size_t> &leaf_widths, const DeviceOpener *open_device, const InitialOpener *open_host,
+                               p2hot_challenger *challenger, const p2hot_fri_params *fp, p2hot_fri_proof *proof) {
+    const size_t n_oracles = leaf_widths.size(), n_instances = instances.size();
+    if (!challenger || challenger->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: the challenger belongs to another context", what);
+    if (!proof || n_instances == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null argument", what);
     // FriParams::hiding changes nothing on the prover's FRI path (it is observed into the transcript by the caller,
     // fri/mod.rs:148, and tells the VERIFIER to strip the salts, fri/verifier.rs:149-151): blinded oracles carry their salt columns
-    P2_TRY(fri_check_params(ctx, fp, log_n));
+    const unsigned log_n = instances[0].log_n;
+    FriRounds rounds;
+    P2_TRY(fri_check_params(ctx, fp, log_n, &rounds));
     const unsigned rate_bits = fp->rate_bits, cap_height = fp->cap_height, log_N = log_n + rate_bits, n_rounds = fp->n_reduction_rounds;
-    const size_t n = (size_t)1 << log_n, N = n << rate_bits, Q = fp->num_query_rounds;
+    const size_t Q = fp->num_query_rounds;
+    if (n_rounds > 32) P2_FAIL(ctx, P2HOT_EINVAL, "%s: more than 32 reduction rounds", what);
+    if (fp->proof_of_work_bits > 64) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof_of_work_bits > 64", what);
     p2hot_fri_proof_layout lay;
-    {
-        std::vector<size_t> widths;
-        for (auto &v : views) widths.push_back(v.leaf_width());
-        if (fri_proof_layout(widths.data(), n_oracles, log_n, fp, &lay) != P2HOT_OK) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: inconsistent parameters");
-    }
+    if (fri_proof_layout(leaf_widths.data(), n_oracles, log_n, fp, &lay) != P2HOT_OK) P2_FAIL(ctx, P2HOT_EINVAL, "%s: inconsistent parameters", what);
     if ((lay.caps_words && !proof->commit_phase_merkle_caps) || !proof->final_poly ||
         (Q && ((lay.initial_leaves_words && !proof->initial_leaves) || (lay.initial_paths_words && !proof->initial_paths) ||
                (lay.step_evals_words && !proof->step_evals) || (lay.step_paths_words && !proof->step_paths))))
-        P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: a proof buffer is null (size them with p2hot_fri_proof_sizes)");
-    const std::vector<OracleView> &oracles = views;
-    // --- the polynomial table of the instance (FriInstanceInfo.batches, fri/structure.rs): device pointers in batch order
-    std::vector<const u64 *> ptrs;
-    std::vector<size_t> offsets(1, 0);
-    std::vector<u64> points;
-    for (size_t i = 0; i < n_batches; ++i) {
-        const p2hot_fri_batch_info &bi = batches[i];
-        if (bi.n_polys && (!bi.oracle_index || !bi.poly_index)) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: batch %zu has null index arrays", i);
-        for (size_t j = 0; j < bi.n_polys; ++j) {
-            const size_t oi = bi.oracle_index[j], pi = bi.poly_index[j];
-            if (oi >= n_oracles || pi >= oracles[oi].W)
-                P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: batch %zu opens polynomial (%zu, %zu) which does not exist", i, oi, pi);
-            ptrs.push_back(oracles[oi].d_coef + pi * oracles[oi].col_coef(log_n));
-        }
-        offsets.push_back(ptrs.size());
-        points.push_back(bi.point[0]);
-        points.push_back(bi.point[1]);
+        P2_FAIL(ctx, P2HOT_EINVAL, "%s: a proof buffer is null (size them with the *_fri_proof_sizes call of this path)", what);
+    // --- device blocks: pointer tables, one final_poly plane pair per instance, round trees (leaves + digests), query staging
+    size_t table_words = 0, plane_words = 0, w_sum = 0;
+    for (auto &in : instances) {
+        table_words += in.ptrs.size();
+        plane_words += (size_t)2 << in.log_n;
     }
-    // --- device blocks: pointer table, final_poly planes, round trees (leaves + digests), query staging
-    size_t leaf_words = 0, dig_words = 0;
-    {
-        size_t m = N;
-        unsigned lm = log_N;
-        for (unsigned r = 0; r < n_rounds; ++r) {
-            const unsigned ab = fp->reduction_arity_bits[r];
-            leaf_words += 2 * m;
-            dig_words += 4 * p2hot_num_digests(lm - ab, cap_height);
-            m >>= ab;
-            lm -= ab;
-        }
-    }
+    for (size_t w : leaf_widths) w_sum += w;
     const unsigned layers0 = log_N - cap_height;
     PoolBuf d_table(ctx), d_planes(ctx), d_leaves(ctx), d_dig(ctx), d_q(ctx);
-    P2_TRY(pool_alloc(ctx, (ptrs.size() ? ptrs.size() : 1) * sizeof(u64 *), &d_table.p));
-    P2_TRY(pool_alloc(ctx, 2 * n * 8, &d_planes.p));
-    P2_TRY(pool_alloc(ctx, (leaf_words ? leaf_words : 1) * 8, &d_leaves.p));
-    P2_TRY(pool_alloc(ctx, (dig_words ? dig_words : 1) * 8, &d_dig.p));
-    // query staging: indices [1 + R][Q] | initial leaves | initial paths | step evals | step paths | rand [Q] | alpha [2] | best | resp | saved challenger
-    const size_t ch_words = (sizeof(fri::Challenger) + 7) / 8;
-    const size_t q_words = Q * (1 + n_rounds) + lay.initial_leaves_words + lay.initial_paths_words + lay.step_evals_words +
-                           lay.step_paths_words + Q + 2 + 1 + 1 + ch_words;
-    P2_TRY(pool_alloc(ctx, q_words * 8, &d_q.p));
-    u64 *d_idx = d_q.u(), *d_il = d_idx + Q * (1 + n_rounds), *d_ip = d_il + lay.initial_leaves_words,
-        *d_se = d_ip + lay.initial_paths_words, *d_sp = d_se + lay.step_evals_words, *d_rand = d_sp + lay.step_paths_words,
-        *d_alpha = d_rand + Q, *d_best = d_alpha + 2, *d_resp = d_best + 1, *d_chsave = d_resp + 1;
+    QueryStaging q;
+    P2_TRY(pool_alloc(ctx, (table_words ? table_words : 1) * sizeof(u64 *), &d_table.p));
+    P2_TRY(pool_alloc(ctx, plane_words * 8, &d_planes.p));
+    P2_TRY(pool_alloc(ctx, (rounds.leaf_words ? rounds.leaf_words : 1) * 8, &d_leaves.p));
+    P2_TRY(pool_alloc(ctx, (rounds.dig_words ? rounds.dig_words : 1) * 8, &d_dig.p));
+    P2_TRY(query_staging_alloc(ctx, Q, n_rounds, lay, &d_q, &q));
     fri::ArityBits ab{};
-    if (n_rounds > 32) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: more than 32 reduction rounds");
-    if (fp->proof_of_work_bits > 64) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: proof_of_work_bits > 64");
-    for (unsigned r = 0; r < n_rounds; ++r) ab.b[r] = (unsigned char)fp->reduction_arity_bits[r];
-    size_t w_sum = 0;
-    for (size_t o = 0; o < n_oracles; ++o) w_sum += oracles[o].leaf_width();
+    for (unsigned r = 0; r < n_rounds; ++r) ab.b[r] = (unsigned char)rounds.round[r].arity_bits;
+    std::vector<const uint64_t *> planes(n_instances);
+    std::vector<unsigned> join_log_n;
+    {
+        u64 *p = d_planes.u();
+        for (size_t i = 0; i < n_instances; ++i) {
+            planes[i] = p;
+            p += (size_t)2 << instances[i].log_n;
+            if (i) join_log_n.push_back(instances[i].log_n);
+        }
+    }
     unsigned long long best = ~0ull;
     u64 pow_next = 0;
     std::vector<u64> idx_for_owners;
@@ -1174,106 +1178,143 @@ static int prove_openings_core(p2hot_ctx *ctx, const p2hot_fri_batch_info *batch
     // stay on the device (the challenger is device-resident), results reach the caller's buffers by asynchronous copies
     // and ONE synchronisation ends the call.
     auto head = [&]() -> int {
-        if (!ptrs.empty())
-            P2_HIP(ctx, hipMemcpyAsync(d_table.p, ptrs.data(), ptrs.size() * sizeof(u64 *), hipMemcpyHostToDevice, ctx->stream));
-        // oracle.rs:186: alpha = challenger.get_extension_challenge()
-        P2_TRY(challenger_step_dev(challenger, nullptr, 0, d_alpha, 2));
-        // oracle.rs:190-213: final_poly = sum_i alpha^(k_i) (F_i - F_i(z_i)) / (X - z_i)
-        P2_TRY(final_poly_core(ctx, (const uint64_t *const *)d_table.p, offsets.data(), n_batches, points.data(), nullptr, d_alpha, log_n,
-                               d_planes.u()));
-        // oracle.rs:215-220 + fri/prover.rs:40-51: final FFT, commit phase; the round trees stay on the device
-        P2_TRY(fri_commit_core(ctx, nullptr, d_planes.u(), log_n, rate_bits, cap_height, fp->reduction_arity_bits, n_rounds,
-                               fp->max_num_query_steps, fp->final_poly_coeff_len, challenger, d_leaves.u(), true, d_dig.u(), true,
-                               proof->commit_phase_merkle_caps, nullptr, proof->final_poly, /*defer_sync=*/true));
+        // A copy from pageable host memory holds the host until the stream has drained.  The first instance's pointer table
+        // therefore goes up before anything is launched (behind the challenger's kernel it would stall the enqueueing of a
+        // launch-bound small proof); a joining instance's goes up immediately before its final_poly, where the wait hides
+        // behind the previous instance's kernels.  Neither copy touches what the challenger reads: the order changes no result.
+        const u64 **tab = (const u64 **)d_table.p;
+        auto upload = [&](const OpeningInstance &in) -> int {
+            if (!in.ptrs.empty())
+                P2_HIP(ctx, hipMemcpyAsync(tab, in.ptrs.data(), in.ptrs.size() * sizeof(u64 *), hipMemcpyHostToDevice, ctx->stream));
+            return P2HOT_OK;
+        };
+        P2_TRY(upload(instances[0]));
+        // oracle.rs:186 (batch_fri/oracle.rs:138): alpha = challenger.get_extension_challenge(), once for every instance
+        P2_TRY(challenger_step_dev(challenger, nullptr, 0, q.alpha, 2));
+        // oracle.rs:190-213: final_poly = sum_i alpha^(k_i) (F_i - F_i(z_i)) / (X - z_i), one per instance (batch_fri/oracle.rs:143-179:
+        // ReducingFactor's count is zero at the start of each, so every instance is the plain prelude with the same alpha)
+        for (size_t i = 0; i < n_instances; ++i) {
+            const OpeningInstance &in = instances[i];
+            if (i) P2_TRY(upload(in));
+            P2_TRY(final_poly_core(ctx, (const uint64_t *const *)tab, in.offsets.data(), in.n_batches(), in.points.data(), nullptr, q.alpha,
+                                   in.log_n, (uint64_t *)planes[i]));
+            tab += in.ptrs.size();
+        }
+        // oracle.rs:215-220 + fri/prover.rs:40-51 (batch_fri/prover.rs:53-62): final FFT, commit phase; the round trees stay on the device
+        const BatchJoin join{planes.data() + 1, join_log_n.data(), n_instances - 1};
+        P2_TRY(fri_commit_core(ctx, nullptr, planes[0], log_n, rate_bits, cap_height, fp->reduction_arity_bits, n_rounds,
+                               fp->max_num_query_steps, fp->final_poly_coeff_len, challenger,
+                               FriCommitOut{.leaves_out = d_leaves.u(), .leaves_on_device = true, .digests_out = d_dig.u(),
+                                            .digests_on_device = true, .caps_out = proof->commit_phase_merkle_caps,
+                                            .final_out = proof->final_poly, .defer_sync = true},
+                               &join));
         // fri/prover.rs:53-58: proof of work, searched on the device; the transcript state before it is kept for the
         // (practically unreachable) case that the searched range holds no witness
-        P2_HIP(ctx, hipMemcpyAsync(d_chsave, challenger->d, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, ctx->stream));
-        return pow_search_dev(ctx, challenger, fp->proof_of_work_bits, (unsigned long long *)d_best, &pow_next);
+        P2_HIP(ctx, hipMemcpyAsync(q.chsave, challenger->d, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, ctx->stream));
+        return pow_search_dev(ctx, challenger, fp->proof_of_work_bits, (unsigned long long *)q.best, &pow_next);
     };
     auto tail = [&]() -> int {
         // prover.rs:197-198: observe the witness, draw the response
-        P2_TRY(challenger_step_dev(challenger, d_best, 1, d_resp, 1));
-        P2_TRY(d2h(ctx, &best, d_best, 8));
+        P2_TRY(challenger_step_dev(challenger, q.best, 1, q.resp, 1));
+        P2_TRY(d2h(ctx, &best, q.best, 8));
         if (Q == 0) return P2HOT_OK;
         // fri/prover.rs:215-220: x_index = rand % n for num_query_rounds challenges; per round x_index >>= arity_bits (:243-253)
-        P2_TRY(challenger_step_dev(challenger, nullptr, 0, d_rand, Q));
-        P2HOT_LAUNCH(fri::query_indices_kernel, dim3(cdiv(Q, 256)), dim3(256), 0, ctx->stream, (const u64 *)d_rand, Q, log_N, ab, n_rounds,
-                     d_idx);
+        P2_TRY(challenger_step_dev(challenger, nullptr, 0, q.rand, Q));
+        P2HOT_LAUNCH(fri::query_indices_kernel, dim3(cdiv(Q, 256)), dim3(256), 0, ctx->stream, (const u64 *)q.rand, Q, log_N, ab, n_rounds,
+                     q.idx);
         P2_LAUNCH_CHECK(ctx);
-        if (proof->query_indices) P2_TRY(d2h(ctx, proof->query_indices, d_idx, Q * 8));
-        if (open_initial) {  // the owners of the rows need the indices on the host
+        if (proof->query_indices) P2_TRY(d2h(ctx, proof->query_indices, q.idx, Q * 8));
+        if (open_host) {  // the owners of the rows need the indices on the host
             idx_for_owners.resize(Q);
-            P2_TRY(d2h(ctx, idx_for_owners.data(), d_idx, Q * 8));
+            P2_TRY(d2h(ctx, idx_for_owners.data(), q.idx, Q * 8));
         }
         // prover.rs:238-241: initial_trees_proof = for every oracle (tree.get(x), tree.prove(x)), all queries per launch.
         // Device staging is oracle-major ([oracle][q][...]); the host layout is query-major (see p2hot.h), fixed by the D2H copies.
         size_t w_off = 0;
-        for (size_t o = 0; o < n_oracles && !open_initial; ++o) {
-            const OracleView &B = oracles[o];
-            P2_TRY(p2hot_gather_rows_dev(ctx, B.d_lde, B.col_lde(), B.N, B.leaf_width(), d_idx, Q, d_il + Q * w_off));
-            P2_TRY(p2hot_merkle_paths_dev(ctx, B.d_dig, log_N, cap_height, d_idx, Q, d_ip + o * Q * 4 * layers0));
-            w_off += B.leaf_width();
+        for (size_t o = 0; o < n_oracles && open_device; ++o) {
+            P2_TRY((*open_device)(o, q.idx, Q, q.leaves + Q * w_off, q.paths + o * Q * 4 * layers0));
+            w_off += leaf_widths[o];
         }
         // prover.rs:242-253: per round (evals = unflatten(tree.get(x >> arity_bits)), tree.prove(x >> arity_bits))
-        size_t ev_off = 0, pa_off = 0, lv = 0, dg = 0, m = N;
-        unsigned lm = log_N;
-        std::vector<size_t> ev_offs, pa_offs, ev_w, pa_w;
         for (unsigned r = 0; r < n_rounds; ++r) {
-            const unsigned abr = fp->reduction_arity_bits[r];
-            const size_t roww = (size_t)2 << abr, layers = lm - abr - cap_height;
-            P2HOT_LAUNCH(fri::gather_rowmajor_kernel, dim3(cdiv(Q * roww, 256)), dim3(256), 0, ctx->stream, (const u64 *)(d_leaves.u() + lv),
-                         roww, m >> abr, (const u64 *)(d_idx + (1 + (size_t)r) * Q), Q, d_se + Q * ev_off, ctx->d_oob);
+            const FriRound &f = rounds.round[r];
+            const u64 *d_idx_r = q.idx + (1 + (size_t)r) * Q;
+            P2HOT_LAUNCH(fri::gather_rowmajor_kernel, dim3(cdiv(Q * f.ev_w, 256)), dim3(256), 0, ctx->stream,
+                         (const u64 *)(d_leaves.u() + f.leaf_off), f.ev_w, f.rows >> f.arity_bits, d_idx_r, Q, q.evals + Q * f.ev_off, ctx->d_oob);
             P2_LAUNCH_CHECK(ctx);
-            if (layers)
-                P2_TRY(p2hot_merkle_paths_dev(ctx, d_dig.u() + dg, lm - abr, cap_height, d_idx + (1 + (size_t)r) * Q, Q, d_sp + Q * pa_off));
-            ev_offs.push_back(ev_off);
-            pa_offs.push_back(pa_off);
-            ev_w.push_back(roww);
-            pa_w.push_back(4 * layers);
-            ev_off += roww;
-            pa_off += 4 * layers;
-            lv += 2 * m;
-            dg += 4 * p2hot_num_digests(lm - abr, cap_height);
-            m >>= abr;
-            lm -= abr;
+            if (f.pa_w)
+                P2_TRY(p2hot_merkle_paths_dev(ctx, d_dig.u() + f.dig_off, f.log_leaves, cap_height, d_idx_r, Q, q.step_paths + Q * f.pa_off));
         }
         // D2H: one strided copy per (oracle | round) turns the oracle-major staging into the query-major proof layout
         w_off = 0;
-        for (size_t o = 0; o < n_oracles && !open_initial; ++o) {
-            const size_t Wb = oracles[o].leaf_width();
-            if (Wb)
-                P2_TRY(d2h_2d(ctx, proof->initial_leaves + w_off, w_sum * 8, d_il + Q * w_off, Wb * 8, Wb * 8, Q));
+        for (size_t o = 0; o < n_oracles && open_device; ++o) {
+            const size_t Wb = leaf_widths[o];
+            if (Wb) P2_TRY(d2h_2d(ctx, proof->initial_leaves + w_off, w_sum * 8, q.leaves + Q * w_off, Wb * 8, Wb * 8, Q));
             if (layers0)
-                P2_TRY(d2h_2d(ctx, proof->initial_paths + o * 4 * layers0, n_oracles * 4 * layers0 * 8, d_ip + o * Q * 4 * layers0,
+                P2_TRY(d2h_2d(ctx, proof->initial_paths + o * 4 * layers0, n_oracles * 4 * layers0 * 8, q.paths + o * Q * 4 * layers0,
                               4 * layers0 * 8, 4 * layers0 * 8, Q));
             w_off += Wb;
         }
-        for (unsigned r = 0; r < n_rounds; ++r) {
-            P2_TRY(d2h_2d(ctx, proof->step_evals + ev_offs[r], ev_off * 8, d_se + Q * ev_offs[r], ev_w[r] * 8, ev_w[r] * 8, Q));
-            if (pa_w[r])
-                P2_TRY(d2h_2d(ctx, proof->step_paths + pa_offs[r], pa_off * 8, d_sp + Q * pa_offs[r], pa_w[r] * 8, pa_w[r] * 8, Q));
+        for (const FriRound &f : rounds.round) {
+            P2_TRY(d2h_2d(ctx, proof->step_evals + f.ev_off, rounds.ev_words * 8, q.evals + Q * f.ev_off, f.ev_w * 8, f.ev_w * 8, Q));
+            if (f.pa_w)
+                P2_TRY(d2h_2d(ctx, proof->step_paths + f.pa_off, rounds.pa_words * 8, q.step_paths + Q * f.pa_off, f.pa_w * 8, f.pa_w * 8, Q));
         }
         return P2HOT_OK;
     };
     int rc = head();
     if (rc == P2HOT_OK) rc = tail();
-    rc = sync_checked(ctx, rc, "prove_openings");
+    rc = sync_checked(ctx, rc, what);
     if (rc == P2HOT_OK && best == ~0ull) {
         // no witness among the first 2^(pow_bits + 5) candidates (probability e^-32): rewind the transcript to before the
         // grind, search the rest of the range with a host check per chunk, and replay the tail
         // (errors go through rc + sync_checked like the main path: the PoolBuf blocks must not return to the cache while
         // enqueued work still references them)
         auto fallback = [&]() -> int {
-            P2_HIP(ctx, hipMemcpyAsync(challenger->d, d_chsave, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, ctx->stream));
-            P2_TRY(pow_continue_host(ctx, challenger, fp->proof_of_work_bits, (unsigned long long *)d_best, pow_next, &best));
+            P2_HIP(ctx, hipMemcpyAsync(challenger->d, q.chsave, sizeof(fri::Challenger), hipMemcpyDeviceToDevice, ctx->stream));
+            P2_TRY(pow_continue_host(ctx, challenger, fp->proof_of_work_bits, (unsigned long long *)q.best, pow_next, &best));
             return tail();
         };
-        rc = sync_checked(ctx, fallback(), "prove_openings");
+        rc = sync_checked(ctx, fallback(), what);
     }
     if (rc == P2HOT_OK) proof->pow_witness = best;
     // a sharded batch: the initial trees' rows and paths come from the ranks that own them
-    if (rc == P2HOT_OK && open_initial && Q) rc = (*open_initial)(idx_for_owners.data(), Q, proof->initial_leaves, proof->initial_paths);
+    if (rc == P2HOT_OK && open_host && Q) rc = (*open_host)(idx_for_owners.data(), Q, proof->initial_leaves, proof->initial_paths);
     return rc;
+}
+
+// One instance over oracles of one degree given as views: the plain path (the trees are on this context, open_initial == NULL)
+// and the sharded one (open_initial serves the rows and paths from the ranks that own them).
+static int prove_openings_views(p2hot_ctx *ctx, const p2hot_fri_batch_info *batches, size_t n_batches, const std::vector<OracleView> &views,
+                                unsigned log_n, p2hot_challenger *challenger, const p2hot_fri_params *fp, p2hot_fri_proof *proof,
+                                const InitialOpener *open_initial) {
+    if (n_batches && !batches) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: null argument");
+    // the polynomial table of the instance (FriInstanceInfo.batches, fri/structure.rs): device pointers in batch order
+    std::vector<OpeningInstance> instance(1);
+    OpeningInstance &in = instance[0];
+    in.log_n = log_n;
+    for (size_t i = 0; i < n_batches; ++i) {
+        const p2hot_fri_batch_info &bi = batches[i];
+        if (bi.n_polys && (!bi.oracle_index || !bi.poly_index)) P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: batch %zu has null index arrays", i);
+        for (size_t j = 0; j < bi.n_polys; ++j) {
+            const size_t oi = bi.oracle_index[j], pi = bi.poly_index[j];
+            if (oi >= views.size() || pi >= views[oi].W)
+                P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings: batch %zu opens polynomial (%zu, %zu) which does not exist", i, oi, pi);
+            in.ptrs.push_back(views[oi].d_coef + pi * views[oi].col_coef(log_n));
+        }
+        in.offsets.push_back(in.ptrs.size());
+        in.points.push_back(bi.point[0]);
+        in.points.push_back(bi.point[1]);
+    }
+    std::vector<size_t> leaf_widths;
+    for (auto &v : views) leaf_widths.push_back(v.leaf_width());
+    const DeviceOpener on_device = [&](size_t o, const u64 *d_idx, size_t Q, u64 *d_rows, u64 *d_paths) -> int {
+        const OracleView &B = views[o];
+        P2_TRY(p2hot_gather_rows_dev(ctx, B.d_lde, B.col_lde(), B.N, B.leaf_width(), d_idx, Q, d_rows));
+        return p2hot_merkle_paths_dev(ctx, B.d_dig, log_n + fp->rate_bits, fp->cap_height, d_idx, Q, d_paths);
+    };
+    return prove_openings_core(ctx, "prove_openings", instance, leaf_widths, open_initial ? nullptr : &on_device, open_initial, challenger,
+                               fp, proof);
 }
 
 // ------------------------------------------------------------------ permutation argument (plonk/prover.rs:356-449)

@@ -1600,30 +1600,76 @@ struct BatchJoin {
     size_t count;
 };
 
+// The reduction rounds of one FRI proof (fri/prover.rs:94-120, :242-253): the geometry that the commit phase, the proof layout
+// and the query rounds share.  Round r folds a codeword of `rows` extension elements by 2^arity_bits; its tree has
+// 2^log_leaves leaves of ev_w words.
+struct FriRound {
+    unsigned arity_bits, log_leaves;
+    size_t rows;
+    size_t leaf_off, dig_off;  // word offsets of the round's leaves / digests in the device-resident round trees
+    size_t ev_off, pa_off;     // word offsets inside one query's step_evals / step_paths
+    size_t ev_w, pa_w;         // words per query: 2 << arity_bits evaluations, 4 * (log_leaves - cap_height) path words
+};
+struct FriRounds {
+    std::vector<FriRound> round;
+    size_t leaf_words = 0, dig_words = 0, ev_words = 0, pa_words = 0;  // totals of the offsets above
+    unsigned log_last = 0;                                            // log2 of the codeword length after the last fold
+};
+
+// ctx == NULL (the context-free *_fri_proof_sizes calls): a bare P2HOT_EINVAL, and only for a schedule that cannot be sized
+static int fri_rounds(p2hot_ctx *ctx, const char *what, unsigned log_n, unsigned rate_bits, unsigned cap_height, const unsigned *arity_bits,
+                      unsigned n_rounds, FriRounds *out) {
+    unsigned lm = log_n + rate_bits;
+    out->round.reserve(std::min(n_rounds, 32u));
+    for (unsigned r = 0; r < n_rounds; ++r) {
+        const unsigned ab = arity_bits[r];
+        if (ctx && (ab == 0 || ab > lm - rate_bits))
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: round %u arity 2^%u does not divide the degree bound", what, r, ab);
+        if (ab > lm || lm - ab < cap_height) {
+            if (!ctx) return P2HOT_EINVAL;
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: round %u tree has fewer leaves than the cap (merkle_tree.rs:195-200)", what, r);
+        }
+        const FriRound f{ab, lm - ab, (size_t)1 << lm, out->leaf_words, out->dig_words, out->ev_words, out->pa_words, (size_t)2 << ab,
+                         4 * (size_t)(lm - ab - cap_height)};
+        out->round.push_back(f);
+        out->leaf_words += 2 * f.rows;
+        out->dig_words += 4 * p2hot_num_digests(f.log_leaves, cap_height);
+        out->ev_words += f.ev_w;
+        out->pa_words += f.pa_w;
+        lm -= ab;
+    }
+    out->log_last = lm;
+    return P2HOT_OK;
+}
+
+// where the commit phase leaves its results; a NULL destination is skipped
+struct FriCommitOut {
+    uint64_t *leaves_out = nullptr;  // the round codewords, interleaved [rows][2], one after the other
+    bool leaves_on_device = false;
+    uint64_t *digests_out = nullptr;  // the round trees' digests
+    bool digests_on_device = false;
+    uint64_t *caps_out = nullptr, *betas_out = nullptr, *final_out = nullptr;  // host
+    bool defer_sync = false;  // the caller synchronises, after everything it enqueues behind the commit phase
+};
+
 // coeffs: host [n][2] interleaved, or (d_planar != NULL) device planes [2][n]
 // max_num_query_steps / final_poly_coeff_len: the Option<usize> arguments of fri_committed_trees (prover.rs:89-90), 0 = None
 static int fri_commit_core(p2hot_ctx *ctx, const uint64_t *coeffs, const uint64_t *d_planar, unsigned log_n,
                            unsigned rate_bits, unsigned cap_height, const unsigned *arity_bits, unsigned n_rounds,
                            unsigned max_num_query_steps, size_t final_poly_coeff_len,
-                           p2hot_challenger *challenger, uint64_t *leaves_out, bool leaves_on_device, uint64_t *digests_out,
-                           bool digests_on_device, uint64_t *caps_out, uint64_t *betas_out, uint64_t *final_out,
-                           bool defer_sync = false, const BatchJoin *join = nullptr) {
+                           p2hot_challenger *challenger, const FriCommitOut &out, const BatchJoin *join = nullptr) {
     if (!ctx || !challenger || challenger->ctx != ctx) return P2HOT_EINVAL;
     P2_TRY(check_log(ctx, log_n + rate_bits, "fri_commit"));
     if ((!coeffs && !d_planar) || (n_rounds && !arity_bits)) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit: null input");
     const size_t n = (size_t)1 << log_n, N = n << rate_bits;
     // validate the schedule before touching the device
     {
-        unsigned lm = log_n + rate_bits, ln = log_n;
-        for (unsigned r = 0; r < n_rounds; ++r) {
-            unsigned ab = arity_bits[r];
-            if (ab == 0 || ab > ln) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit: round %u arity 2^%u does not divide the degree bound", r, ab);
-            if (lm - ab < cap_height)
-                P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit: round %u tree has fewer leaves than the cap (merkle_tree.rs:195-200)", r);
-            lm -= ab;
-            ln -= ab;
-        }
+        FriRounds schedule;
+        P2_TRY(fri_rounds(ctx, "fri_commit", log_n, rate_bits, cap_height, arity_bits, n_rounds, &schedule));
     }
+    uint64_t *leaves_out = out.leaves_out, *digests_out = out.digests_out, *caps_out = out.caps_out, *betas_out = out.betas_out;
+    uint64_t *const final_out = out.final_out;
+    const bool leaves_on_device = out.leaves_on_device, digests_on_device = out.digests_on_device, defer_sync = out.defer_sync;
     // one grow-only scratch block, carved up (no per-call hipMalloc / hipFree): stage [n][2], two coefficient plane
     // pairs [2][n], values [2][N], interleaved leaves [N][2], digests (<= N of them), cap, beta
     const size_t cap_words = (size_t)4 << cap_height;
@@ -1757,8 +1803,9 @@ extern "C" int p2hot_fri_commit(p2hot_ctx *ctx, const uint64_t *coeffs, unsigned
                                 uint64_t *caps_out, uint64_t *betas_out, uint64_t *final_out) {
     if (ctx && !coeffs) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit: null coefficients");
     return fri_commit_core(ctx, coeffs, nullptr, log_n, rate_bits, cap_height, arity_bits, n_rounds, max_num_query_steps,
-                           final_poly_coeff_len, challenger, leaves_out, false, digests_out, false, caps_out, betas_out,
-                           final_out);
+                           final_poly_coeff_len, challenger,
+                           FriCommitOut{.leaves_out = leaves_out, .digests_out = digests_out, .caps_out = caps_out, .betas_out = betas_out,
+                                        .final_out = final_out});
 }
 
 extern "C" int p2hot_fri_commit_dev(p2hot_ctx *ctx, const uint64_t *d_coeffs_planar, unsigned log_n, unsigned rate_bits,
@@ -1768,8 +1815,10 @@ extern "C" int p2hot_fri_commit_dev(p2hot_ctx *ctx, const uint64_t *d_coeffs_pla
                                     int digests_on_device, uint64_t *caps_out, uint64_t *betas_out, uint64_t *final_out) {
     if (ctx && !d_coeffs_planar) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit_dev: null coefficients");
     return fri_commit_core(ctx, nullptr, d_coeffs_planar, log_n, rate_bits, cap_height, arity_bits, n_rounds,
-                           max_num_query_steps, final_poly_coeff_len, challenger, d_leaves_out, true, digests_out,
-                           digests_on_device != 0, caps_out, betas_out, final_out);
+                           max_num_query_steps, final_poly_coeff_len, challenger,
+                           FriCommitOut{.leaves_out = d_leaves_out, .leaves_on_device = true, .digests_out = digests_out,
+                                        .digests_on_device = digests_on_device != 0, .caps_out = caps_out, .betas_out = betas_out,
+                                        .final_out = final_out});
 }
 
 // ------------------------------------------------------------------ prove_openings prelude

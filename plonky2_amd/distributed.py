@@ -22,6 +22,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .fri.oracle import PROOF_BUFFERS, fri_batch_infos, fri_params, fri_proof_buffers
 
 COSET_SHIFT = 14293326489335486720
 
@@ -361,30 +362,18 @@ class GroupCommit:
     def prove_openings(self, batches, commits, challenger, rate_bits, cap_height, reduction_arity_bits, proof_of_work_bits,
                        num_query_rounds):
         """p2hot_group_prove_openings: flat proof buffers as a dict (layout: include/p2hot.h, p2hot_fri_proof)"""
-        arity = [int(a) for a in reduction_arity_bits]
-        ab = (C.c_uint * max(len(arity), 1))(*arity)
-        fp = _lib.FriParams(rate_bits, cap_height, proof_of_work_bits, num_query_rounds, ab, len(arity), 0, 0, 0)
-        keep, infos = [], (_lib.FriBatchInfo * max(len(batches), 1))()
-        for k, (point, polys) in enumerate(batches):
-            oi = (C.c_uint32 * max(len(polys), 1))(*[o for o, _ in polys])
-            pi = (C.c_uint32 * max(len(polys), 1))(*[p for _, p in polys])
-            keep += [oi, pi]
-            infos[k].point[0], infos[k].point[1] = int(point[0]), int(point[1])
-            infos[k].oracle_index, infos[k].poly_index, infos[k].n_polys = oi, pi, len(polys)
+        fp, _ = fri_params(rate_bits, cap_height, reduction_arity_bits, proof_of_work_bits, num_query_rounds)
+        keep = []
+        infos = fri_batch_infos(batches, keep)
         hs = (C.c_void_p * len(commits))(*[c["handle"] for c in commits])
         lay = _lib.FriProofLayout()
         rc = self.lib.p2hot_group_fri_proof_sizes(hs, len(commits), C.byref(fp), C.byref(lay))
         if rc != _lib.OK:
             raise _lib.P2HotError(rc, "inconsistent FRI parameters")
-        names = ("caps", "final_poly", "initial_leaves", "initial_paths", "step_evals", "step_paths")
-        bufs = {k: np.zeros(max(1, getattr(lay, k + "_words")), dtype=np.uint64) for k in names}
-        qidx = np.zeros(max(1, num_query_rounds), dtype=np.uint64)
-        proof = _lib.FriProof(bufs["caps"].ctypes.data, bufs["final_poly"].ctypes.data, 0, qidx.ctypes.data,
-                              bufs["initial_leaves"].ctypes.data, bufs["initial_paths"].ctypes.data,
-                              bufs["step_evals"].ctypes.data, bufs["step_paths"].ctypes.data)
+        bufs, qidx, proof = fri_proof_buffers(lay, num_query_rounds)
         self._check(self.lib.p2hot_group_prove_openings(self._h, infos, len(batches), hs, len(commits), challenger._h,
                                                         C.byref(fp), C.byref(proof)))
-        out = {k: bufs[k][:getattr(lay, k + "_words")] for k in names}
+        out = {k: bufs[k][:getattr(lay, k + "_words")] for k in PROOF_BUFFERS}
         out["pow_witness"], out["query_indices"] = int(proof.pow_witness), [int(x) for x in qidx[:num_query_rounds]]
         return out
 

@@ -316,6 +316,43 @@ def final_poly_device(batches, oracles, alpha, engine=None):
     return out
 
 
+PROOF_BUFFERS = ("caps", "final_poly", "initial_leaves", "initial_paths", "step_evals", "step_paths")
+
+
+def fri_params(rate_bits, cap_height, reduction_arity_bits, proof_of_work_bits, num_query_rounds, max_num_query_steps=None,
+               final_poly_coeff_len=None):
+    """(p2hot_fri_params, arity bits as a list); the struct keeps its arity array alive"""
+    arity = [int(a) for a in reduction_arity_bits]
+    ab = (C.c_uint * max(len(arity), 1))(*arity)
+    return _lib.FriParams(rate_bits, cap_height, proof_of_work_bits, int(num_query_rounds), ab, len(arity), 0, max_num_query_steps or 0,
+                          final_poly_coeff_len or 0), arity
+
+
+def fri_batch_infos(batches, keep):
+    """p2hot_fri_batch_info[] for FriBatchInfo objects or (point, polynomials) pairs; the index arrays the structs point to are
+    appended to `keep`, which the caller holds until the library call has returned"""
+    infos = (_lib.FriBatchInfo * max(len(batches), 1))()
+    for k, b in enumerate(batches):
+        b = b if isinstance(b, FriBatchInfo) else FriBatchInfo(*b)
+        oi = (C.c_uint32 * max(len(b.polynomials), 1))(*[o for o, _ in b.polynomials])
+        pi = (C.c_uint32 * max(len(b.polynomials), 1))(*[p for _, p in b.polynomials])
+        keep += [oi, pi]
+        infos[k].point[0], infos[k].point[1] = b.point
+        infos[k].oracle_index, infos[k].poly_index, infos[k].n_polys = oi, pi, len(b.polynomials)
+    return infos
+
+
+def fri_proof_buffers(lay, Q):
+    """zeroed host buffers of the sizes in `lay` (None: one word each, for a call that will refuse its arguments) and the
+    p2hot_fri_proof over them: (bufs, qidx, proof)"""
+    bufs = {k: np.zeros(max(1, getattr(lay, k + "_words") if lay is not None else 1), dtype=np.uint64) for k in PROOF_BUFFERS}
+    qidx = np.zeros(max(1, Q), dtype=np.uint64)
+    proof = _lib.FriProof(bufs["caps"].ctypes.data, bufs["final_poly"].ctypes.data, 0, qidx.ctypes.data,
+                          bufs["initial_leaves"].ctypes.data, bufs["initial_paths"].ctypes.data,
+                          bufs["step_evals"].ctypes.data, bufs["step_paths"].ctypes.data)
+    return bufs, qidx, proof
+
+
 def prove_openings(batches, oracles, challenger, rate_bits, cap_height, reduction_arity_bits, proof_of_work_bits,
                    num_query_rounds, engine=None, timing=None, final_poly_coeff_len=None, max_num_query_steps=None):
     """PolynomialBatch::prove_openings + fri_proof (oracle.rs:176-237, fri/prover.rs:24-82): one p2hot_prove_openings
@@ -326,30 +363,17 @@ def prove_openings(batches, oracles, challenger, rate_bits, cap_height, reductio
     `timing` (a dict): total synchronised wall milliseconds of the call under "prove_openings"."""
     import time
     eng = engine or oracles[0].engine
-    arity = [int(a) for a in reduction_arity_bits]
-    R, Q = len(arity), int(num_query_rounds)
-    ab = (C.c_uint * max(R, 1))(*arity)
-    fp = _lib.FriParams(rate_bits, cap_height, proof_of_work_bits, Q, ab, R, 0, max_num_query_steps or 0,
-                        final_poly_coeff_len or 0)
-    keep = []  # index arrays referenced by the batch structs
-    infos = (_lib.FriBatchInfo * max(len(batches), 1))()
-    for k, b in enumerate(batches):
-        oi = (C.c_uint32 * max(len(b.polynomials), 1))(*[o for o, _ in b.polynomials])
-        pi = (C.c_uint32 * max(len(b.polynomials), 1))(*[p for _, p in b.polynomials])
-        keep += [oi, pi]
-        infos[k].point[0], infos[k].point[1] = b.point
-        infos[k].oracle_index, infos[k].poly_index, infos[k].n_polys = oi, pi, len(b.polynomials)
+    fp, arity = fri_params(rate_bits, cap_height, reduction_arity_bits, proof_of_work_bits, num_query_rounds, max_num_query_steps,
+                           final_poly_coeff_len)
+    Q = int(num_query_rounds)
+    keep = []
+    infos = fri_batch_infos(batches, keep)
     handles = _handles(oracles)
     lay = _lib.FriProofLayout()
     rc = eng.lib.p2hot_fri_proof_sizes(handles, len(oracles), C.byref(fp), C.byref(lay))
     if rc != _lib.OK:
         raise _lib.P2HotError(rc, "inconsistent FRI parameters")
-    bufs = {k: np.zeros(max(1, getattr(lay, k + "_words")), dtype=np.uint64)
-            for k in ("caps", "final_poly", "initial_leaves", "initial_paths", "step_evals", "step_paths")}
-    qidx = np.zeros(max(1, Q), dtype=np.uint64)
-    proof = _lib.FriProof(bufs["caps"].ctypes.data, bufs["final_poly"].ctypes.data, 0, qidx.ctypes.data,
-                          bufs["initial_leaves"].ctypes.data, bufs["initial_paths"].ctypes.data,
-                          bufs["step_evals"].ctypes.data, bufs["step_paths"].ctypes.data)
+    bufs, qidx, proof = fri_proof_buffers(lay, Q)
     t0 = time.perf_counter()
     eng.check(eng.lib.p2hot_prove_openings(eng.ctx, infos, len(batches), handles, len(oracles), challenger._h, C.byref(fp),
                                            C.byref(proof)))

@@ -398,6 +398,41 @@ def test_one_instance_one_group_equals_prove_openings(eng, ora):
     assert write_fri_proof(pp) == write_fri_proof(proof)
 
 
+def test_batch_pow_witness_outside_the_first_search_range(eng, ora, monkeypatch):
+    """The batch path shares the opening-proof core with p2hot_prove_openings, and with it the rewind of the transcript when the
+    range searched on the device holds no witness (tests/test_prove_openings.py, test_pow_witness_outside_the_first_search_range).
+    Forced here by shrinking the range to 2^3 candidates (P2HOT_POW_RANGE_LOG) over the accepted proof of
+    test_batch_prove_openings_validation: the proof's bytes and the transcript afterwards are unchanged, and equal the restated prover's."""
+    from plonky2_amd.batch_fri import BatchFriOracle, FriInstanceInfo
+    from plonky2_amd.iop.challenger import Challenger
+    from tests.wire_format import write_fri_proof
+    rng = np.random.default_rng(8)
+    degree_bits, rate_bits, cap_height, arity, pow_bits, nq, z = [7, 5], 1, 2, [2], 9, 3, [3, 4]
+    polys = [rand_field(rng, 1 << 7), rand_field(rng, 1 << 5)]
+    instances = [[(z, [(0, 0)])], [(z, [(0, 1)])]]
+    oracle = BatchFriOracle.from_coeffs(polys, rate_bits, False, cap_height, engine=eng)
+    runs = []
+    for rng_log in (None, "-6"):
+        if rng_log is None:
+            monkeypatch.delenv("P2HOT_POW_RANGE_LOG", raising=False)
+        else:
+            monkeypatch.setenv("P2HOT_POW_RANGE_LOG", rng_log)
+        c = Challenger(eng)
+        c.observe_elements(np.arange(5, dtype=np.uint64))
+        proof = BatchFriOracle.prove_openings(degree_bits, [FriInstanceInfo(b) for b in instances], [oracle], c, rate_bits, cap_height, arity,
+                                              pow_bits, nq, engine=eng)
+        runs.append((proof, c.get_n_challenges(3)))
+    (p0, t0), (p1, t1) = runs
+    assert p0["pow_witness"] >= 8            # the forced run did leave its first range (the seed was picked for this)
+    assert write_fri_proof(p0) == write_fri_proof(p1) and p0["query_indices"] == p1["query_indices"] and t0 == t1
+    oc = ora.Challenger()
+    oc.observe_elements(np.arange(5, dtype=np.uint64))
+    exp = ref.prove_openings(degree_bits, instances, [ref.BatchFriOracle(polys, rate_bits, cap_height)], oc, rate_bits, cap_height, arity,
+                             pow_bits, nq)
+    _assert_same_proof(p1, exp)
+    assert oc.get_n_challenges(3) == t1
+
+
 # ------------------------------------------------------------------ 6. validation
 def _commit_raw(eng, degrees, rate_bits, cap_height, flags=0, seed=1):
     rng = np.random.default_rng(seed)
