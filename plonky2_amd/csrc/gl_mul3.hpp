@@ -16,7 +16,10 @@
 //                                                                               (goldilocks_field.rs:402-415)
 // Since round 6 the hot kernels (Poseidon S-boxes, the limb NTT's general multiplies) run mul3cg / mul1cg below: the same 14
 // instructions with steps 5-7 (three carry adds) replaced by three co-issued v_mov_b32 and two chained addends; mul3 / mul2 / mad3
-// stay for the plonk and FRI kernels.
+// stay for the plonk and FRI kernels.  The one-permutation-per-lane Poseidon (leaf sponge, Merkle levels) runs mul3cx / mul1cx: mul3cg's
+// steps 1-9, then the carry c as ONE add under a lane mask (EXEC = c & saved EXEC) and the borrow b -- one lane in 2^32 -- behind a scalar
+// branch: 11 vector instructions + 2.7 scalar ones per product (the headline step with and without: profiles/exec_fixups_ab.txt).  What the
+// scalar ALU costs on this chip, and the all-scalar form that lost because of it: profiles/exec_fixups_ubench.txt.
 // Temporaries are fixed VGPR/SGPR pairs (declared as clobbers) because inline-asm operands cannot
 // name the halves of a 64-bit register pair.  The emulator build runs these blocks either through its instruction
 // interpreter (asm_block.h: the same template strings, hazard- and clobber-checked) or, by default, as gl::mul.
@@ -245,6 +248,66 @@ __device__ __forceinline__ u64 mul1cg(u64 a, u64 b) {
            (P2_I([xa0], "v", (u32)a), P2_I([xa1], "v", (u32)(a >> 32)), P2_I([ya0], "v", (u32)b), P2_I([ya1], "v", (u32)(b >> 32))),
            ("v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "s40", "s41", "s42", "s43"));
     return ra;
+}
+
+// ---- mul3cx / mul1cx: the same product with the reduction's tail e = c - b split by how often each flag is set (the Poseidon
+// S-boxes of the one-permutation-per-lane kernels) ------
+// Steps 1-9 are mul3cg's; step 9 (u = t + T.lo * (2^32 - 1), carry c) writes the result pair.  The value is u + (c - b)(2^32 - 1):
+//   c (set in about half the lanes)      one add of 2^32 - 1 under EXEC = c & saved EXEC (v_mad_u64_u32 r = 1 * -1 + r)
+//   b (set with probability 2^-32 on random operands)   the b pairs of the three streams are ORed on the scalar ALU and a scalar branch
+//                                        skips the fix-up: under EXEC = b & saved EXEC, r += (2^32 - 1)^2 + (2^32 - 1) + 1 = -(2^32 - 1) mod 2^64
+//                                        (three adds with inline constants: the path needs no constant in a register)
+// 11 vector instructions per product (8 at full price) + 2.7 scalar ones, where mul3cg has 14 (11).  A scalar instruction is not free on
+// gfx950 at the leaf sponge's four waves per SIMD -- about 2 cycles each -- so the form that also takes c & ~b and b & ~c on the scalar ALU
+// and applies both under masks (5 scalar instructions per product) LOSES to mul3cg there; this split form wins
+// (profiles/exec_fixups_ubench.txt).  Wait states: a scalar read of a VALU-written SGPR pair and a VALU after a scalar EXEC write need
+// none (the hazard table lists neither; hipcc emits v_cmp -> s_and_saveexec -> VALU back to back).  EXEC is saved at the top of a block
+// and restored before its end, every mask is ANDed with the saved copy (lanes retired early stay retired), and nothing after an EXEC
+// write reads another lane.  The emulator build always takes gl::mul: its interpreter knows neither scalar instructions nor EXEC.
+#define P2_CX9(P, P0, P1, M, M0, M1, N, N0, N1, T, T0, T1, C1, C2, a0, a1, b0, b1, r0) "v_mad_u64_u32 %[" r0 "], " C2 ", " T0 ", -1, " M "\n\t"
+#define P2_CXC(P, P0, P1, M, M0, M1, N, N0, N1, T, T0, T1, C1, C2, a0, a1, b0, b1, r0) \
+    "s_and_b64 exec, " C2 ", s[52:53]\n\tv_mad_u64_u32 %[" r0 "], " C2 ", 1, -1, %[" r0 "]\n\t"
+#define P2_CXB(P, P0, P1, M, M0, M1, N, N0, N1, T, T0, T1, C1, C2, a0, a1, b0, b1, r0)                                              \
+    "s_and_b64 exec, " C1 ", s[52:53]\n\tv_mad_u64_u32 %[" r0 "], " C2 ", -1, -1, %[" r0 "]\n\tv_mad_u64_u32 %[" r0 "], " C2 ", 1, -1, %[" r0 "]\n\t" \
+    "v_lshl_add_u64 %[" r0 "], %[" r0 "], 0, 1\n\t"
+#define P2_CX_SAVE "s_mov_b64 s[52:53], exec\n\t"
+#define P2_CX_REST "s_mov_b64 exec, s[52:53]\n\t"
+
+__device__ __forceinline__ void mul3cx(const u64 a[3], const u64 b[3], u64 r[3]) {
+#ifdef P2HOT_EMU
+    for (int k = 0; k < 3; ++k) r[k] = mul(a[k], b[k]);
+#else
+    u64 ra, rb, rc;
+    P2_ASM(P2_CX_SAVE P2_CROW(P2_CG0) P2_CROW(P2_CG1) P2_CROW(P2_CG2) P2_CROW(P2_CG3) P2_CROW(P2_CG4) P2_CROW(P2_CG5) P2_CROW(P2_CG6)
+               P2_CROW(P2_CG7) P2_CROW(P2_CG8) P2_CROW(P2_CX9) P2_CROW(P2_CXC) P2_CX_REST
+           "s_or_b64 s[42:43], s[40:41], s[44:45]\n\ts_or_b64 s[42:43], s[42:43], s[48:49]\n\ts_cbranch_scc0 1f\n\t"
+               P2_CROW(P2_CXB) P2_CX_REST "1:\n\t",
+           (P2_O([ra0], "=&v", ra), P2_O([rb0], "=&v", rb), P2_O([rc0], "=&v", rc)),
+           (P2_I([xa0], "v", (u32)a[0]), P2_I([xa1], "v", (u32)(a[0] >> 32)), P2_I([ya0], "v", (u32)b[0]),
+            P2_I([ya1], "v", (u32)(b[0] >> 32)), P2_I([xb0], "v", (u32)a[1]), P2_I([xb1], "v", (u32)(a[1] >> 32)),
+            P2_I([yb0], "v", (u32)b[1]), P2_I([yb1], "v", (u32)(b[1] >> 32)), P2_I([xc0], "v", (u32)a[2]),
+            P2_I([xc1], "v", (u32)(a[2] >> 32)), P2_I([yc0], "v", (u32)b[2]), P2_I([yc1], "v", (u32)(b[2] >> 32))),
+           (P2_CG_CLOBBERS3, "s52", "s53", "scc"));
+    r[0] = ra;
+    r[1] = rb;
+    r[2] = rc;
+#endif
+}
+
+// one stream: the wait states of mul1cg's row 7 -> 8 stay; the scalar reads of c and b need none
+__device__ __forceinline__ u64 mul1cx(u64 a, u64 b) {
+#ifdef P2HOT_EMU
+    return mul(a, b);
+#else
+    u64 ra;
+    P2_ASM(P2_CX_SAVE P2_CA1(P2_CG0) P2_CA1(P2_CG1) P2_CA1(P2_CG2) P2_CA1(P2_CG3) P2_CA1(P2_CG4) P2_CA1(P2_CG5) P2_CA1(P2_CG6) P2_CA1(P2_CG7) P2_NOP
+               P2_CA1(P2_CG8) P2_CA1(P2_CX9) P2_CA1(P2_CXC) P2_CX_REST "s_cmp_lg_u64 s[40:41], 0\n\ts_cbranch_scc0 1f\n\t"
+                   P2_CA1(P2_CXB) P2_CX_REST "1:\n\t",
+           (P2_O([ra0], "=&v", ra)),
+           (P2_I([xa0], "v", (u32)a), P2_I([xa1], "v", (u32)(a >> 32)), P2_I([ya0], "v", (u32)b), P2_I([ya1], "v", (u32)(b >> 32))),
+           ("v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "s40", "s41", "s42", "s43", "s52", "s53", "scc"));
+    return ra;
+#endif
 }
 
 // ---- fold3: three MDS-row recombinations in one interleaved stream ------------------------------

@@ -284,7 +284,7 @@ __global__ void field_selftest_kernel(const u64 *a, const u64 *b, size_t count, 
     // the other hand-written streams against the compiler's arithmetic, one flag bit each:
     // 2 = the low-register single stream, 4 = the power-of-two twiddle multiplies of the radix-8 butterflies (ntt.hpp),
     // 8 / 16 = the MDS row recombinations fold1 / fold3 on accumulators below 2^63, 32 = the two-stream mul2 (64: reserved, never set), 128 = gl::mul_add, 256 = gl::mad3, 512 = gl::mul3cg / mul1cg,
-    // 1024 = the wide recombinations fold1w / fold3w
+    // 1024 = the wide recombinations fold1w / fold3w, 2048 = gl::mul3cx / mul1cx (the carry under a lane mask, the borrow behind a scalar branch)
     if (gl::canon(gl::mul1_lowregs(x, y)) != gl::canon(gl::mul(x, y))) ok |= 2;
 #define P2_CHK_POW2(S)                                                                                              \
     if (gl::canon(ntt::mul_pow2_asm<S>(x)) != gl::canon(gl::mul(x, (S) < 64 ? 1ull << ((S) & 63) : 0xFFFFFFFFull << (((S) - 64) & 31)))) \
@@ -334,6 +334,17 @@ __global__ void field_selftest_kernel(const u64 *a, const u64 *b, size_t count, 
         for (int k = 0; k < 3; ++k)
             if (gl::canon(y3[k]) != gl::canon(gl::add(al3[k], gl::mul(ah3[k], 1ull << 32)))) ok |= 1024;
         if (gl::canon(gl::fold1w(x, y)) != gl::canon(gl::add(x, gl::mul(y, 1ull << 32)))) ok |= 1024;
+    }
+    {  // 2048 = gl::mul3cx / mul1cx: (x, y) and (y, y) in each of the three stream positions, two other products beside them
+        const u64 z = x ^ 0x9E3779B97F4A7C15ull;
+        const u64 a3[3][3] = {{x, y, z}, {y, z, x}, {z, x, y}}, b3[3][3] = {{y, y, x}, {y, x, y}, {x, y, y}};
+        for (int j = 0; j < 3; ++j) {
+            u64 r3[3];
+            gl::mul3cx(a3[j], b3[j], r3);
+            for (int k = 0; k < 3; ++k)
+                if (gl::canon(r3[k]) != gl::canon(gl::mul(a3[j][k], b3[j][k]))) ok |= 2048;
+        }
+        if (gl::canon(gl::mul1cx(x, y)) != gl::canon(gl::mul(x, y)) || gl::canon(gl::mul1cx(y, y)) != gl::canon(gl::mul(y, y))) ok |= 2048;
     }
     out[2 * count + t] = gl::canon(rr[0]);
     out[5 * count + t] = ok;

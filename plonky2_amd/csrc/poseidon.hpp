@@ -70,14 +70,23 @@ __device__ __forceinline__ u32 opaque_zero() {
 #endif
 }
 
-// The S-box products run the carry-free multiply streams gl::mul3cg / mul1cg (gl_mul3.hpp: 14 instructions, 3 of them co-issued
-// moves; the streams measured against them: profiles/r06_sbox_hybrid_ab.txt).
+// The S-box products run the carry-free multiply streams of gl_mul3.hpp.  The one-permutation-per-lane permutation below (leaf sponge,
+// Merkle levels, permutation batches) takes gl::mul3cx / mul1cx: the reduction's carry as one add under a lane mask, its borrow behind a
+// scalar branch -- 11 vector instructions per product where gl::mul3cg / mul1cg have 14 (profiles/exec_fixups_ab.txt).  The cooperative
+// kernels (poseidon4.hpp, poseidon16.hpp: latency-bound launches with lane exchanges between the rounds) and the Poseidon gate's
+// constraints (gates.hpp) keep the mul3cg / mul1cg forms: sbox7_asm, sbox7_x3, sbox_layer.
 // x^7 of one word with the hand-scheduled multiply (the partial rounds' single S-box)
 __device__ __forceinline__ u64 sbox7_asm(u64 x) {
     u64 x2 = gl::mul1cg(x, x);
     u64 x4 = gl::mul1cg(x2, x2);
     u64 x3 = gl::mul1cg(x, x2);
     return gl::mul1cg(x3, x4);
+}
+__device__ __forceinline__ u64 sbox7_cx(u64 x) {
+    u64 x2 = gl::mul1cx(x, x);
+    u64 x4 = gl::mul1cx(x2, x2);
+    u64 x3 = gl::mul1cx(x, x2);
+    return gl::mul1cx(x3, x4);
 }
 
 // x^7 of three independent words at once: x2 = x*x; (x3 = x*x2 and x4 = x2*x2 are independent); x7 = x3*x4
@@ -91,10 +100,24 @@ __device__ __forceinline__ void sbox7_x3(u64 &a, u64 &b, u64 &c) {
     b = x[1];
     c = x[2];
 }
+__device__ __forceinline__ void sbox7_x3cx(u64 &a, u64 &b, u64 &c) {
+    u64 x[3] = {a, b, c}, x2[3], x3[3], x4[3];
+    gl::mul3cx(x, x, x2);
+    gl::mul3cx(x, x2, x3);
+    gl::mul3cx(x2, x2, x4);
+    gl::mul3cx(x3, x4, x);
+    a = x[0];
+    b = x[1];
+    c = x[2];
+}
 
 __device__ __forceinline__ void sbox_layer(u64 s[12]) {  // poseidon.rs:712-718
 #pragma unroll
     for (int i = 0; i < 12; i += 3) sbox7_x3(s[i], s[i + 1], s[i + 2]);
+}
+__device__ __forceinline__ void sbox_layer_cx(u64 s[12]) {
+#pragma unroll
+    for (int i = 0; i < 12; i += 3) sbox7_x3cx(s[i], s[i + 1], s[i + 2]);
 }
 
 // Wave-uniform small constant that the optimiser must not see through: keeps c * x as ONE
@@ -327,7 +350,7 @@ static_assert(pass4_rows_fit(), "(MD)^3 M: a four-application row would overflow
 template <bool FIRST = false>
 __device__ __forceinline__ void partial_rounds4(u64 s[12], u64 c1, u64 c2, u64 c3, u64 cn) {
     u32 xl[12], xh[12];
-    const u64 z0 = FIRST ? s[0] : sbox7_asm(s[0]);  // (not FIRST) round 0's scalar is already in s[0]
+    const u64 z0 = FIRST ? s[0] : sbox7_cx(s[0]);  // (not FIRST) round 0's scalar is already in s[0]
     xl[0] = (u32)z0;
     xh[0] = (u32)(z0 >> 32);
 #pragma unroll
@@ -341,7 +364,7 @@ __device__ __forceinline__ void partial_rounds4(u64 s[12], u64 c1, u64 c2, u64 c
         al += (u64)xl[j] * P2_POSEIDON_M1_ROW0[j];
         ah += (u64)xh[j] * P2_POSEIDON_M1_ROW0[j];
     }
-    const u64 s1 = sbox7_asm(gl::fold1(al, ah));
+    const u64 s1 = sbox7_cx(gl::fold1(al, ah));
     const u32 s1l = (u32)s1, s1h = (u32)(s1 >> 32);
     al = (u64)s1l * MDS1.v[0] + (u32)c2;
     ah = (u64)s1h * MDS1.v[0] + (c2 >> 32);
@@ -350,7 +373,7 @@ __device__ __forceinline__ void partial_rounds4(u64 s[12], u64 c1, u64 c2, u64 c
         al += (u64)xl[j] * MDM.v[j];
         ah += (u64)xh[j] * MDM.v[j];
     }
-    const u64 s2 = sbox7_asm(gl::fold1(al, ah));
+    const u64 s2 = sbox7_cx(gl::fold1(al, ah));
     const u32 s2l = (u32)s2, s2h = (u32)(s2 >> 32);
     al = (u64)s1l * MDM.v[0] + (u64)s2l * MDS1.v[0] + (u32)c3;
     ah = (u64)s1h * MDM.v[0] + (u64)s2h * MDS1.v[0] + (c3 >> 32);
@@ -359,7 +382,7 @@ __device__ __forceinline__ void partial_rounds4(u64 s[12], u64 c1, u64 c2, u64 c
         al += (u64)xl[j] * MDMDM.v[j];
         ah += (u64)xh[j] * MDMDM.v[j];
     }
-    const u64 s3 = sbox7_asm(gl::fold1(al, ah));  // row 0 of (MD)^2 M: below 2^25 * 2^32
+    const u64 s3 = sbox7_cx(gl::fold1(al, ah));  // row 0 of (MD)^2 M: below 2^25 * 2^32
     const u32 s3l = (u32)s3, s3h = (u32)(s3 >> 32);
 #pragma unroll
     for (int g = 0; g < 12; g += 3) {
@@ -397,7 +420,7 @@ __device__ __forceinline__ void partial_rounds4(u64 s[12], u64 c1, u64 c2, u64 c
 // 4-instruction additions less per permutation than adding it afterwards: -0.3 % cycles, profiles/r06_partial_rounds_ab.txt).
 __device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, const u64 *cv) {
     u32 xl[12], xh[12];
-    const u64 z0 = sbox7_asm(s[0]);  // round 0's scalar is already in s[0]: the previous pass fused it into its row 0
+    const u64 z0 = sbox7_cx(s[0]);  // round 0's scalar is already in s[0]: the previous pass fused it into its row 0
     xl[0] = (u32)z0;
     xh[0] = (u32)(z0 >> 32);
 #pragma unroll
@@ -411,7 +434,7 @@ __device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, const
         al += (u64)xl[j] * P2_POSEIDON_M1_ROW0[j];
         ah += (u64)xh[j] * P2_POSEIDON_M1_ROW0[j];
     }
-    const u64 s1 = sbox7_asm(gl::fold1(al, ah));
+    const u64 s1 = sbox7_cx(gl::fold1(al, ah));
     const u32 s1l = (u32)s1, s1h = (u32)(s1 >> 32);
     al = (u64)s1l * MDS1.v[0] + (u32)c2;
     ah = (u64)s1h * MDS1.v[0] + (c2 >> 32);
@@ -420,7 +443,7 @@ __device__ __forceinline__ void partial_rounds3(u64 s[12], u64 c1, u64 c2, const
         al += (u64)xl[j] * MDM.v[j];
         ah += (u64)xh[j] * MDM.v[j];
     }
-    const u64 s2 = sbox7_asm(gl::fold1(al, ah));
+    const u64 s2 = sbox7_cx(gl::fold1(al, ah));
     const u32 s2l = (u32)s2, s2h = (u32)(s2 >> 32);
 #pragma unroll
     for (int g = 0; g < 12; g += 3) {
@@ -456,13 +479,13 @@ __device__ inline void permute(u64 s[12], unsigned out_groups = 0xFu, int out_si
     int round = 0;
 #pragma unroll 1
     for (int k = 0; k < 3; ++k, ++round) {
-        sbox_layer(s);
+        sbox_layer_cx(s);
         mds_layer(s, RC_SPLIT + 24 * (round + 1));
     }
     // round 3's S-box layer; its MDS and partial rounds 4..6 in ONE dense pass (partial_rounds4<true>); no constant is fused into
     // round 3's MDS -- the batched partial rounds add their scalars themselves (the passive part of the partial-round constants
     // is pushed forward through the MDS at table-generation time, see the generator)
-    sbox_layer(s);
+    sbox_layer_cx(s);
     partial_rounds4<true>(s, P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 4], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 5],
                           P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 6], P2_POSEIDON_PUSHED_ROUND_CONSTANTS[12 * 7]);
     round = 7;
@@ -480,10 +503,10 @@ __device__ inline void permute(u64 s[12], unsigned out_groups = 0xFu, int out_si
     round = 26;
 #pragma unroll 1
     for (int k = 0; k < 3; ++k, ++round) {
-        sbox_layer(s);
+        sbox_layer_cx(s);
         mds_layer(s, RC_SPLIT + 24 * (round + 1));
     }
-    sbox_layer(s);
+    sbox_layer_cx(s);
     mds_layer(s, nullptr, out_groups, out_single);
 }
 

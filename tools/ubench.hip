@@ -6,7 +6,8 @@
 // clocks to its power budget, so that column is only comparable within one run.  The yardstick the bench uses comes from
 // tools/ubench_pmc.sh: the same probes under `rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU`, i.e. TRUE
 // shader cycles per instruction and the clock each probe ran at (tools/ubench_summarize.py -> profiles/r04_ubench.json).
-// usage: ubench [--waves N] [--only substring] [--json]   (N = resident waves per SIMD: 8 default, 4 = the leaf sponge's)
+// usage: ubench [--waves N] [--only substring] [--json]   (N = resident waves per SIMD: 8 default, 4 = the leaf sponge's;
+//        --only "fix " = the masked-add family alone; UBENCH_ONLY in the environment is --only's default, for tools/ubench_pmc.sh)
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -430,6 +431,84 @@ __global__ void __launch_bounds__(256) k(uint64_t *out, uint32_t seed, uint64_t 
               "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", \
               "v48", "v49", "v50", "v51"
 #define XCLOB2 XCLOB, "v52", "v53", "v54", "v55", "v56"
+// ---- carry fix-ups as lane-masked adds: can the scalar ALU take the carry / borrow bookkeeping of gl::mul3cg and gl::fold3w for free?
+// The real instruction streams (same dependences, same SGPR producer / consumer distances) on explicit registers: stream set = 8 VGPRs
+// from p (P, M, N, T pairs), 4 SGPRs from c (two carry pairs), result pair r; operands a = (v48, v49), b = (v51, v50), al = v[52:53].
+// s[36:37] keeps EXEC over a block, s[38:39] = {1, -1} = -(2^32 - 1) mod 2^64, s[40:41] is the one mask temporary.
+//   OP 300  gl::mul3cg as shipped: e = c - b by v_cndmask + v_subb, u + (e << 32) - e by v_add_u32 + v_mad_i64_i32   (14 VALU / product)
+//   OP 301  step CG9 writes the result; plus = c & ~b, minus = b & ~c on the scalar ALU, two adds under EXEC = mask     (12 VALU + 5 scalar)
+//   OP 302  the same with the minus add behind a scalar branch (b is set with probability 2^-32 on random operands)     (11 VALU + 6 scalar)
+//   OP 303  gl::fold3w as shipped (6 VALU / row)              OP 304  both carries as one masked add each (4 VALU + 3 scalar / row)
+//   OP 305  30 multiply-adds + 3 x (5 scalar mask ops, 2 masked adds): the product's ratio on a multiply-add stream (36 VALU per trip)
+//   OP 306  32 multiply-adds (= OP 132): the yardstick of one run of `--only "fix "`
+// A scalar instruction is not free at 4 waves per SIMD (305 against 306), so two further forms split e = c - b by how often each flag
+// is set: the carry c (half the lanes) stays vector work or takes ONE mask write, the borrow b (probability 2^-32 on random operands)
+// is tested once for the three streams and fixed up behind a branch:
+//   OP 307  c by v_cndmask (-1 / 0) + v_mad_u64_u32 (e * 1 + u); one test + branch per three products                  (12 VALU + 1 scalar)
+//   OP 308  c as one add under EXEC = c & saved per stream; the same test + branch                                     (11 VALU + 2.7 scalar)
+// Mask fill: the operands of a probe do not change from trip to trip, so neither do its masks.  301 / 302 / 305 count their plus mask
+// inside the loop (305 its minus mask too); the others replay one product / row behind the loop, outside the timed part, and count
+// the third stream's flags there.  Products: c in half the lanes, b in none.  305: v[54:55] / v[58:59] hold bit 31 of the lane's
+// operand and its complement at bit 63, and (2^32 - 1)^2 + that carries exactly where the bit is set: plus and minus masks half full each.
+#define VP(p, k) "v[" #p "+" #k "]"
+#define VQ(p, k) "v[" #p "+" #k ":" #p "+" #k "+1]"
+#define SQ(c, k) "s[" #c "+" #k ":" #c "+" #k "+1]"
+#define E_CG0(p, c, r) "v_mov_b32 " VP(p, 7) ", 0\n\t"
+#define E_CG1(p, c, r) "v_mad_u64_u32 " VQ(p, 0) ", " SQ(c, 0) ", v48, v51, 0\n\t"
+#define E_CG2(p, c, r) "v_mov_b32 " VP(p, 6) ", " VP(p, 1) "\n\t"
+#define E_CG3(p, c, r) "v_mad_u64_u32 " VQ(p, 2) ", " SQ(c, 0) ", v49, v51, " VQ(p, 6) "\n\t"
+#define E_CG4(p, c, r) "v_mad_u64_u32 " VQ(p, 4) ", " SQ(c, 2) ", v48, v50, " VQ(p, 2) "\n\t"
+#define E_CG5(p, c, r) "v_mov_b32 " VP(p, 6) ", " VP(p, 5) "\n\t"
+#define E_CG6(p, c, r) "v_mad_u64_u32 " VQ(p, 6) ", " SQ(c, 0) ", v49, v50, " VQ(p, 6) "\n\t"
+#define E_CG7(p, c, r) "v_subb_co_u32 " VP(p, 2) ", " SQ(c, 0) ", " VP(p, 0) ", " VP(p, 7) ", " SQ(c, 2) "\n\t"
+#define E_CG8(p, c, r) "v_subb_co_u32 " VP(p, 3) ", " SQ(c, 0) ", " VP(p, 4) ", 0, " SQ(c, 0) "\n\t"
+#define E_CG9(p, c, r) "v_mad_u64_u32 " VQ(p, 2) ", " SQ(c, 2) ", " VP(p, 6) ", -1, " VQ(p, 2) "\n\t"
+#define E_CG10(p, c, r) "v_cndmask_b32 " VP(p, 4) ", 0, 1, " SQ(c, 2) "\n\t"
+#define E_CG11(p, c, r) "v_subb_co_u32 " VP(p, 4) ", " SQ(c, 0) ", " VP(p, 4) ", 0, " SQ(c, 0) "\n\t"
+#define E_CG12(p, c, r) "v_add_u32 " VP(p, 3) ", " VP(p, 3) ", " VP(p, 4) "\n\t"
+#define E_CG13(p, c, r) "v_mad_i64_i32 " VQ(r, 0) ", " SQ(c, 0) ", " VP(p, 4) ", -1, " VQ(p, 2) "\n\t"
+#define E_CG9R(p, c, r) "v_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 2) ", " VP(p, 6) ", -1, " VQ(p, 2) "\n\t"
+#define E_MINUS(p, c, r) "s_and_b64 exec, " SQ(c, 0) ", s[36:37]\n\tv_lshl_add_u64 " VQ(r, 0) ", " VQ(r, 0) ", 0, s[38:39]\n\t"
+// plus is taken first: its masked multiply-add reuses the c pair as its (dead) carry-out, so minus must already be in the b pair
+#define E_FIX(p, c, r) "s_andn2_b64 s[40:41], " SQ(c, 2) ", " SQ(c, 0) "\n\ts_andn2_b64 " SQ(c, 0) ", " SQ(c, 0) ", " SQ(c, 2) "\n\t" \
+                       "s_and_b64 exec, s[40:41], s[36:37]\n\tv_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 2) ", 1, -1, " VQ(r, 0) "\n\t" E_MINUS(p, c, r)
+#define E_FIXBR(p, c, r) "s_andn2_b64 s[40:41], " SQ(c, 2) ", " SQ(c, 0) "\n\ts_andn2_b64 " SQ(c, 0) ", " SQ(c, 0) ", " SQ(c, 2) "\n\t" \
+                         "s_cbranch_scc0 1f\n\t" E_MINUS(p, c, r) "1:\n\t"                                                             \
+                         "s_and_b64 exec, s[40:41], s[36:37]\n\tv_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 2) ", 1, -1, " VQ(r, 0) "\n\t"
+#define E_FW1(p, c, r) "v_mad_u64_u32 " VQ(p, 0) ", " SQ(c, 0) ", v49, -1, v[52:53]\n\t"
+#define E_FW2(p, c, r) "v_cndmask_b32 " VP(p, 2) ", 0, -1, " SQ(c, 0) "\n\t"
+#define E_FW3(p, c, r) "v_mad_u64_u32 " VQ(p, 0) ", " SQ(c, 0) ", " VP(p, 2) ", 1, " VQ(p, 0) "\n\t"
+#define E_FW4(p, c, r) "v_add_co_u32 " VP(p, 1) ", " SQ(c, 0) ", " VP(p, 1) ", v48\n\t"
+#define E_FW6(p, c, r) "v_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 0) ", " VP(p, 2) ", 1, " VQ(p, 0) "\n\t"
+#define E_FW1R(p, c, r) "v_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 0) ", v49, -1, v[52:53]\n\t"
+#define E_FW4R(p, c, r) "v_add_co_u32 " VP(r, 1) ", " SQ(c, 0) ", " VP(r, 1) ", v48\n\t"
+#define E_FWM(p, c, r) "s_and_b64 exec, " SQ(c, 0) ", s[36:37]\n\tv_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 2) ", 1, -1, " VQ(r, 0) "\n\t"
+#define E_CGM(p, c, r) "v_cndmask_b32 " VP(p, 4) ", 0, -1, " SQ(c, 2) "\n\t"
+#define E_CGA(p, c, r) "v_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 2) ", " VP(p, 4) ", 1, " VQ(p, 2) "\n\t"
+#define E_CMASK(p, c, r) "s_and_b64 exec, " SQ(c, 2) ", s[36:37]\n\tv_mad_u64_u32 " VQ(r, 0) ", " SQ(c, 2) ", 1, -1, " VQ(r, 0) "\n\t"
+// the borrow's path: any b bit in the three streams?  (the b pairs are SQ(c, 0) of the sets 24, 28, 44)
+#define E_BTEST(SAVE) "s_or_b64 s[40:41], s[24:25], s[28:29]\n\ts_or_b64 s[40:41], s[40:41], s[44:45]\n\ts_cbranch_scc0 1f\n\t" SAVE \
+                      "s_mov_b32 s38, 1\n\ts_mov_b32 s39, -1\n\t" E3(E_MINUS) E_REST "1:\n\t"
+#define E3(ST) ST(16, 24, 40) ST(24, 28, 42) ST(32, 44, 44)
+#define E_SAVE "s_mov_b64 s[36:37], exec\n\ts_mov_b32 s38, 1\n\ts_mov_b32 s39, -1\n\t"
+#define E_REST "s_mov_b64 exec, s[36:37]\n\t"
+#define E_HEAD E3(E_CG0) E3(E_CG1) E3(E_CG2) E3(E_CG3) E3(E_CG4) E3(E_CG5) E3(E_CG6) E3(E_CG7) E3(E_CG8)
+#define E_MUL3_OLD E_HEAD E3(E_CG9) E3(E_CG10) E3(E_CG11) E3(E_CG12) E3(E_CG13)
+#define E_MUL3_MASK E_HEAD E3(E_CG9R) E3(E_FIX) E_REST
+#define E_MUL3_MASKBR E_HEAD E3(E_CG9R) E3(E_FIXBR) E_REST
+#define E_MUL3_SPLIT E_HEAD E3(E_CG9) E3(E_CGM) E3(E_CGA) E_BTEST("s_mov_b64 s[36:37], exec\n\t")
+#define E_MUL3_SPLITX "s_mov_b64 s[36:37], exec\n\t" E_HEAD E3(E_CG9R) E3(E_CMASK) E_REST E_BTEST("")
+#define E_FOLD3W_OLD E3(E_FW1) E3(E_FW2) E3(E_FW3) E3(E_FW4) E3(E_FW2) E3(E_FW6)
+#define E_FOLD3W_MASK E3(E_FW1R) E3(E_FWM) E_REST E3(E_FW4R) E3(E_FWM) E_REST
+#define E_MAD10(c) MADP(18) MADP(22) MADP(26) MADP(30) MADP(34) MADP(38) MADP(18) MADP(22) \
+                   "v_mad_u64_u32 v[26:27], " SQ(c, 0) ", v56, v56, v[58:59]\n\tv_mad_u64_u32 v[30:31], " SQ(c, 2) ", v56, v56, v[54:55]\n\t"
+#define E_MADFIX(p, c, r) E_MAD10(c) E_FIX(p, c, r) E_REST  // EXEC whole again before the next ten multiply-adds
+#define XCLOB3 XCLOB2, "v58", "v59", "scc", "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s36", "s37", "s38", "s39", "s40", "s41", "s44", "s45", "s46", "s47"
+// mask populations (asm outputs %0, %1), so that a run can state how full the masks were: the last plus mask, the third stream's pairs
+#define E_POP "s_bcnt1_i32_b64 %0, s[40:41]\n\t"
+#define E_POPB(k) "s_bcnt1_i32_b64 %" #k ", s[44:45]\n\t"
+#define E_POPC(k) "s_bcnt1_i32_b64 %" #k ", s[46:47]\n\t"
+#define E_MAD_MASKS "v_mov_b32 v56, -1\n\tv_mov_b32 v54, 0\n\tv_and_b32 v55, 0x80000000, v48\n\tv_mov_b32 v58, 0\n\tv_xor_b32 v59, 0x80000000, v55\n\t"
 #define P_INIT(r) "v_mov_b32 v" #r ", %0\n\t"
 #define P_SUM(r) "v_xor_b32 %0, %0, v" #r "\n\t"
 
@@ -438,6 +517,8 @@ __global__ void __launch_bounds__(256) kx(uint64_t *out, uint32_t seed, uint64_t
     uint32_t t = threadIdx.x + blockIdx.x * blockDim.x;
     uint32_t c = t * 2654435761u + seed;
     asm volatile(XR(P_INIT) "v_mov_b32 v48, %0\n\tv_mov_b32 v49, %0\n\tv_mov_b32 v50, 0x3f800001\n\tv_mov_b32 v51, %0\n\ts_mov_b32 s20, 77\n\ts_mov_b32 s21, 0\n\tv_mov_b32 v52, 0\n\tv_mov_b32 v53, 0x3ff00000\n\tv_mov_b32 v54, 1\n\tv_mov_b32 v55, 0x3ff00000\n\tv_mov_b32 v56, %0" ::"v"(c) : XCLOB2);
+    if (OP == 305) asm volatile(E_MAD_MASKS ::: XCLOB3);
+    uint32_t pop = 0, pop2 = 0;
     uint64_t t0 = __builtin_readcyclecounter();
 #pragma unroll 1
     for (int it = 0; it < ITERS / 4; ++it) {
@@ -512,12 +593,25 @@ __global__ void __launch_bounds__(256) kx(uint64_t *out, uint32_t seed, uint64_t
         if (OP == 166) asm volatile(XP(P_MAD_CNDM) ::: XCLOB2);
         if (OP == 159) asm volatile(XP(P_FMA64_ONLY) ::: XCLOB2);
         if (OP == 168) asm volatile(XP(P_FMA64_ADDU) ::: XCLOB2);
+        if (OP == 300) asm volatile(E_MUL3_OLD E_MUL3_OLD ::: XCLOB3);
+        if (OP == 301) asm volatile(E_SAVE E_MUL3_MASK E_MUL3_MASK E_POP : "=s"(pop) :: XCLOB3);
+        if (OP == 302) asm volatile(E_SAVE E_MUL3_MASKBR E_MUL3_MASKBR E_POP : "=s"(pop) :: XCLOB3);
+        if (OP == 303) asm volatile(E_FOLD3W_OLD E_FOLD3W_OLD E_FOLD3W_OLD E_FOLD3W_OLD ::: XCLOB3);
+        if (OP == 304) asm volatile(E_SAVE E_FOLD3W_MASK E_FOLD3W_MASK E_FOLD3W_MASK E_FOLD3W_MASK ::: XCLOB3);
+        if (OP == 305) asm volatile(E_SAVE E3(E_MADFIX) E_POP E_POPB(1) : "=s"(pop), "=s"(pop2) :: XCLOB3);
+        if (OP == 306) asm volatile(XP(P_MAD_ONLY) ::: XCLOB);
+        if (OP == 307) asm volatile(E_MUL3_SPLIT E_MUL3_SPLIT ::: XCLOB3);
+        if (OP == 308) asm volatile(E_MUL3_SPLITX E_MUL3_SPLITX ::: XCLOB3);
         if (OP == 167) asm volatile(XP4A(P_MAD4) XP4A(P_ADD4) XP4B(P_MAD4) XP4B(P_ADD4) XP4C(P_MAD4) XP4C(P_ADD4) XP4D(P_MAD4) XP4D(P_ADD4) ::: XCLOB2);
     }
     uint64_t t1 = __builtin_readcyclecounter();
+    // one more product / row of the probes that do not count inside the loop: carry c and borrow b of the third stream; both carries of a row
+    if (OP == 300 || OP == 307 || OP == 308) asm volatile(E_HEAD E3(E_CG9) E_POPC(0) E_POPB(1) : "=s"(pop), "=s"(pop2) :: XCLOB3);
+    if (OP == 303) asm volatile(E3(E_FW1) E_POPB(0) E3(E_FW2) E3(E_FW3) E3(E_FW4) E_POPB(1) E3(E_FW2) E3(E_FW6) : "=s"(pop), "=s"(pop2) :: XCLOB3);
+    if (OP == 304) asm volatile(E_SAVE E3(E_FW1R) E_POPB(0) E3(E_FWM) E_REST E3(E_FW4R) E_POPB(1) E3(E_FWM) E_REST : "=s"(pop), "=s"(pop2) :: XCLOB3);
     uint32_t s = 0;
     asm volatile(XR(P_SUM) : "+v"(s)::XCLOB);
-    out[t] = s;
+    out[t] = s | (uint64_t)(pop | pop2 << 8) << 32;
     if ((threadIdx.x & 63) == 0) ticks[t >> 6] = t1 - t0;
 }
 
@@ -620,9 +714,21 @@ void run(const char *name, int per_iter = 8) {
     double avg = 0;
     for (int i = 0; i < blocks * threads / 64; ++i) avg += (double)host_ticks[i];
     avg /= (blocks * threads / 64);
+    double lanes = -1, lanes2 = -1;  // the masked-add probes: mean population of the two masks a probe counts, over the waves
+    if (X && OP >= 300) {
+        static uint64_t host_out[256 * 8 * 4];
+        lanes = lanes2 = 0;
+        for (int w = 0; w < blocks * threads / 64; ++w) {
+            (void)hipMemcpy(&host_out[w], d + (size_t)w * 64, 8, hipMemcpyDeviceToHost);
+            lanes += (double)(host_out[w] >> 32 & 0xff);
+            lanes2 += (double)(host_out[w] >> 40 & 0xff);
+        }
+        lanes /= blocks * threads / 64;
+        lanes2 /= blocks * threads / 64;
+    }
     if (g_json)
-        printf("{\"op\": %d, \"name\": \"%s\", \"waves_per_simd\": %d, \"ms\": %.4f, \"wave_insts_per_simd\": %.0f, \"per_iter\": %d}\n", OP, name,
-               g_waves, best, inst_per_simd, per_iter);
+        printf("{\"op\": %d, \"name\": \"%s\", \"waves_per_simd\": %d, \"ms\": %.4f, \"wave_insts_per_simd\": %.0f, \"per_iter\": %d, \"mask_lanes\": %.1f, \"mask2_lanes\": %.1f}\n", OP, name,
+               g_waves, best, inst_per_simd, per_iter, lanes, lanes2);
     else
         printf("%-18s %7.3f ms  %5.2f cyc/inst/SIMD by wall@2.4GHz(assumed) | %5.2f ticks/inst by s_memtime (ticks/wave %.0f)\n", name, best,
                cycles / inst_per_simd, avg / ((X ? ITERS / 4 : ITERS) * (double)per_iter * waves_per_simd), avg);
@@ -636,6 +742,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--only") && i + 1 < argc) g_only = argv[++i];
         else if (!strcmp(argv[i], "--json")) g_json = true;
     }
+    if (!g_only && getenv("UBENCH_ONLY") && *getenv("UBENCH_ONLY")) g_only = getenv("UBENCH_ONLY");
     if (g_waves < 1 || g_waves > 8) g_waves = 8;
     hipDeviceProp_t p;
     (void)hipGetDeviceProperties(&p, 0);
@@ -769,6 +876,16 @@ int main(int argc, char **argv) {
     run<159, true>("x fma_f64 only", 32);
     run<168, true>("x fma_f64+add_u32 1:1", 32);
     run<167, true>("x mad64 x4 / add,sub x4 runs", 32);
+    // carry fix-ups as masked adds: per_iter = products (rows) per loop trip, so the columns read cycles per PRODUCT (ROW) per SIMD
+    run<306, true>("fix yardstick: mad64 only per VALU", 32);
+    run<300, true>("fix mul3cg per product", 6);
+    run<301, true>("fix mul3 masked adds per product", 6);
+    run<302, true>("fix mul3 masked adds, minus branched per product", 6);
+    run<307, true>("fix mul3 c vector, b branched per product", 6);
+    run<308, true>("fix mul3 c masked add, b branched per product", 6);
+    run<303, true>("fix fold3w per row", 12);
+    run<304, true>("fix fold3w masked adds per row", 12);
+    run<305, true>("fix mad64 x30 + 3 x (5 scalar, 2 masked) per VALU", 36);
     if (g_waves == 4) {
         run_y<207>("y adds only (1024-thread WG)", 64);
         run_y<208>("y mad64 only (1024-thread WG)", 64);

@@ -1,6 +1,7 @@
 #!/bin/bash
 # On the GPU box: tools/ubench at 4 and 8 resident waves per SIMD, plain (wall time) and under rocprofv3 --pmc, so that every
 # probe gets TRUE shader cycles per instruction and the clock it ran at (tooling).  -> gpurun_out/<tag>_ubench.json
+# UBENCH_ONLY="fix " in the environment restricts every run to the probes whose name holds that substring (tools/ubench reads it).
 TAG=${1:-r04}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp

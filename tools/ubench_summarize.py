@@ -6,6 +6,7 @@ Per probe and per occupancy (4 / 8 waves per SIMD): the wall time of the un-prof
   clock_ghz         cycles / kernel duration
   cyc_per_inst      cycles * 1024 SIMDs / SQ_INSTS_VALU            (true shader cycles per wave64 instruction per SIMD)
   valu_busy         SQ_ACTIVE_INST_VALU * 4 / (1024 * cycles)       (quad-cycles the VALU worked / SIMD cycles)
+  cyc_per_unit      cycles / wave_insts_per_simd                    (per unit the probe counts itself in: the "fix" family's products / rows)
 Instruction classes (what bench.py prices a kernel's instruction histogram with) are the medians of their members."""
 import csv
 import glob
@@ -58,6 +59,9 @@ def load(w):
     out = {}
     for name, d in wall.items():
         e = {"ms_unprofiled": d["ms"], "wave_insts_per_simd": d["wave_insts_per_simd"]}
+        for k in ("mask_lanes", "mask2_lanes"):
+            if d.get(k, -1) >= 0:
+                e[k] = d[k]
         if name in acc:
             ids = sorted(dur[name])[1:] or sorted(dur[name])  # the first launch of a probe is the warm-up
             def mean(cn):
@@ -71,6 +75,7 @@ def load(w):
             insts = mean("SQ_INSTS_VALU")
             e.update({"ms_under_pmc": ms, "cycles": cycles, "clock_ghz": cycles / (ms * 1e6) if ms else 0.0,
                       "sq_insts_valu": insts, "cyc_per_inst": cycles * SIMDS / insts if insts else 0.0,
+                      "cyc_per_unit": cycles / d["wave_insts_per_simd"],
                       "valu_busy": mean("SQ_ACTIVE_INST_VALU") * 4 / (SIMDS * cycles) if cycles else 0.0,
                       "wait_inst_any_over_wave_cycles": mean("SQ_WAIT_INST_ANY") / mean("SQ_WAVE_CYCLES") if mean("SQ_WAVE_CYCLES") else 0.0})
         out[name] = e
@@ -93,9 +98,9 @@ def main(tag):
     json.dump(res, open(os.path.join(G, "%s_ubench.json" % tag), "w"), indent=1)
     for w, o in res["occupancy"].items():
         print(w, {k: (round(v["cyc_per_inst_median"], 2), round(v["min"], 2), round(v["max"], 2), round(v["clock_ghz_median"], 2)) for k, v in o["classes"].items()})
-        for n in ("mix hash_leaves", "mix limb_ntt", "v_mad_u64_u32", "v_add_u32"):
+        for n in ["mix hash_leaves", "mix limb_ntt", "v_mad_u64_u32", "v_add_u32"] + sorted(n for n in o["probes"] if n.startswith("fix ")):
             p = o["probes"].get(n, {})
-            print("  ", n, {k: round(p[k], 3) for k in ("ms_unprofiled", "ms_under_pmc", "clock_ghz", "cyc_per_inst", "valu_busy") if k in p})
+            print("  ", n, {k: round(p[k], 3) for k in ("ms_unprofiled", "ms_under_pmc", "clock_ghz", "cyc_per_inst", "cyc_per_unit", "valu_busy", "mask_lanes", "mask2_lanes") if k in p})
 
 
 if __name__ == "__main__":
