@@ -281,7 +281,8 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * p2hot_batch_coeffs / _rows / _paths / _digests / _subgroup_values, p2hot_eval_openings, p2hot_prove_openings, p2hot_partial_products,
  * p2hot_quotient_chunks, p2hot_quotient_polys, p2hot_quotient_polys_lookup, p2hot_lookup_polys, p2hot_cols_concat, p2hot_gate_sums,
  * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_stark_lookup_polys, p2hot_stark_ctl_polys,
- * p2hot_stark_quotient_polys, p2hot_stark_constraint_accs, p2hot_stark_quotient_polys_air, p2hot_ctx_trim, p2hot_batch_oracle_commit,
+ * p2hot_stark_quotient_polys, p2hot_stark_constraint_accs, p2hot_stark_quotient_polys_air, p2hot_gate_sums_programs,
+ * p2hot_quotient_polys_gate_programs, p2hot_quotient_polys_lookup_gate_programs, p2hot_ctx_trim, p2hot_batch_oracle_commit,
  * p2hot_batch_oracle_coeffs / _rows / _paths / _digests, p2hot_batch_prove_openings.  p2hot_batch_free / p2hot_batch_oracle_free / p2hot_cols_free may be called from any thread at any time (a
  * Drop, a finaliser): the block cache has its own lock.  Everything else -- the *_dev building blocks, p2hot_fri_commit,
  * p2hot_fri_pow, p2hot_challenger_* -- enqueues on the context's stream without a guard: the CALLER serialises those with
@@ -624,8 +625,9 @@ int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2hot_cols *b, 
  *                   inter_prod - prod, and the walk goes on from the WIRES over the next d - 1 points (clipped at N); last
  *                   evaluation_value - eval.  The library computes the domain and the weights w_k = x_k / N itself
  *                                                                                                       (coset_interpolation.rs:251-298, :553-580)
- * Every other gate of the reference that has constraints of its own stays the caller's (the host gate_sums of the entry points
- * below): LookupGate / LookupTableGate have none, so only user-defined gates do.  Kinds 8..15 and above 21 are P2HOT_EUNSUPPORTED. */
+ * LookupGate / LookupTableGate have no constraints of their own; every other gate -- a user-defined one -- travels as a gate
+ * program ("gate programs" below) or stays the caller's (the host gate_sums of the entry points below).  Kinds 8..15 and above 21
+ * are P2HOT_EUNSUPPORTED. */
 enum { P2HOT_GATE_NOOP, P2HOT_GATE_CONSTANT, P2HOT_GATE_PUBLIC_INPUT, P2HOT_GATE_ARITHMETIC,
        P2HOT_GATE_ARITHMETIC_EXT, P2HOT_GATE_MUL_EXT, P2HOT_GATE_BASE_SUM, P2HOT_GATE_POSEIDON };
 enum { P2HOT_GATE_POSEIDON_MDS = 16, P2HOT_GATE_REDUCING, P2HOT_GATE_REDUCING_EXT, P2HOT_GATE_RANDOM_ACCESS,
@@ -792,6 +794,55 @@ int p2hot_stark_quotient_polys_air(p2hot_ctx *ctx, const p2hot_batch *trace, con
                                    unsigned constraint_degree, const uint64_t *alphas, unsigned num_challenges,
                                    const p2hot_air_program *program, const uint64_t *public_inputs,
                                    uint64_t *values_out, p2hot_cols **chunks_out);
+
+/* ---------------------------------------------------------------- gate programs: the constraints of user-defined gates (D = 2)
+ * A gate the table of P2HOT_GATE_* does not hold arrives as data: its eval_unfiltered_base_one as a p2hot_air_program (the same
+ * p2hot_air_insn, the same operand packing) read with the GATE's frame and interpreted at every point of the quotient coset
+ * (csrc/gate_program.hpp):
+ *   P2HOT_AIR_LOCAL       wire column c of the row (vars.local_wires[c])
+ *   P2HOT_AIR_GATE_CONST  the gate's own local_constants[c]: constants column num_selectors + num_lookup_selectors + c (gate.rs:179)
+ *   P2HOT_AIR_PUBLIC      public_inputs_hash[i] of the gate set, i < num_publics <= 4
+ *   P2HOT_AIR_CONST, P2HOT_AIR_TEMP  as in a constraint program;  P2HOT_AIR_NEXT is not valid here
+ * An extension-algebra gate is written over pairs of base wires with W = 7.  Ops: ADD, SUB, MUL and CONSTRAINT.  The j-th CONSTRAINT
+ * of a program, in program order, is constraint j of that gate -- every gate's constraints start at index 0
+ * (vanishing_poly.rs:722-725) -- and is weighted by alpha^j (reduce_with_powers, not the STARK consumer's Horner form):
+ *   gate_sums[a][i] += filter_g(x_i) sum_j alpha_a^j c_{g,j}(x_i)
+ * with row, selector_index and [group_first, group_end) as in p2hot_gate.  Kind 5 stays P2HOT_EINVAL in a STARK's program.
+ * The three entry points below are p2hot_gate_sums, p2hot_quotient_polys_gates and p2hot_quotient_polys_lookup_gates argument for
+ * argument plus the programs; `gates` still supplies num_selectors, num_lookup_selectors, public_inputs_hash and the gates the
+ * library knows (it may hold none), the host gate_sums residual is still added on top, and num_programs == 0 is exactly the
+ * entry point without programs.  Launch order: the gate kernels, the program kernel (ONE launch for all programs of the call), the
+ * lookup kernel, the permutation kernel.  Hashers as in the entry points without programs.
+ * Checked before anything is enqueued, the message names the program and the instruction, *chunks_out is NULL on failure.
+ * P2HOT_EINVAL: programs null with num_programs > 0; a program array null with a nonzero count; row outside its group; a group of
+ * more than 256 gates; selector_index >= num_selectors; a wire index beyond the wires commitment; a gate constant that reaches
+ * sigmas_first_col; a NEXT operand or an unknown operand kind; num_publics > 4; a public, constant, temp or dst index beyond its
+ * count; a temp read before any instruction wrote it; a row that appears twice among the programs or also as a descriptor of the
+ * gate set (it would be summed twice); a constraint whose degree -- LOCAL, GATE_CONST 1; PUBLIC, CONST 0; ADD, SUB the larger;
+ * MUL the sum -- plus the filter's (group_end - group_first - 1, and 1 more when num_selectors > 1: gate.rs:326-333) exceeds
+ * quotient_degree_factor + 1, the max_degree of gates/selectors.rs:101-160.  P2HOT_EUNSUPPORTED: an op outside the four (the
+ * three filtered consumer ops among them); num_temps above p2hot_air_max_temps().  A program of num_insns == 0 is valid: a gate
+ * without constraints. */
+#define P2HOT_AIR_GATE_CONST 5u
+typedef struct p2hot_gate_program { uint32_t row, selector_index, group_first, group_end;   /* as in p2hot_gate */
+                                    p2hot_air_program program; } p2hot_gate_program;
+int p2hot_gate_sums_programs(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                             const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,
+                             uint64_t *out_host, const p2hot_gate_program *programs, unsigned num_programs);
+int p2hot_quotient_polys_gate_programs(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                       const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
+                                       unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                       unsigned num_challenges, const uint64_t *const *gate_sums, const p2hot_gate_set *gates,
+                                       uint64_t *values_out, p2hot_cols **chunks_out, const p2hot_gate_program *programs,
+                                       unsigned num_programs);
+int p2hot_quotient_polys_lookup_gate_programs(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
+                                              size_t sigmas_first_col, const p2hot_batch *zs_partial_products_lookups, const uint64_t *k_is,
+                                              unsigned num_routed, unsigned quotient_degree_factor, const uint64_t *betas,
+                                              const uint64_t *gammas, const uint64_t *alphas, unsigned num_challenges,
+                                              const uint64_t *const *gate_sums, unsigned num_lu_slots, unsigned num_lut_slots,
+                                              unsigned num_luts, size_t lookup_selectors_first_col, const uint64_t *deltas,
+                                              const uint64_t *lut_re_poly_evals, const p2hot_gate_set *gates, uint64_t *values_out,
+                                              p2hot_cols **chunks_out, const p2hot_gate_program *programs, unsigned num_programs);
 
 /* ================================================================ batch FRI: polynomials of several degrees, one tree, one proof
  * plonky2/src/batch_fri/{oracle,prover}.rs over hash/batch_merkle_tree.rs.  Poseidon configuration, one GPU, blinding = false: a

@@ -314,11 +314,25 @@ pub struct P2hotAirProgram {
     pub num_publics: u32,
 }
 
+/// p2hot_gate_program: a user-defined gate's `eval_unfiltered_base_one` as a program over the gate's frame (wires, the gate's own
+/// constants, `public_inputs_hash`), placed like a `P2hotGate`.  Deriving the program from a Rust `Gate` is the caller's: the shim has
+/// no tracer for `eval_unfiltered_base_one` yet.
+#[repr(C)]
+pub struct P2hotGateProgram {
+    pub row: u32,
+    pub selector_index: u32,
+    pub group_first: u32,
+    pub group_end: u32,
+    pub program: P2hotAirProgram,
+}
+
 pub const P2HOT_AIR_LOCAL: u32 = 0;
 pub const P2HOT_AIR_NEXT: u32 = 1;
 pub const P2HOT_AIR_PUBLIC: u32 = 2;
 pub const P2HOT_AIR_CONST: u32 = 3;
 pub const P2HOT_AIR_TEMP: u32 = 4;
+/// the gate's own `local_constants[c]`; valid in a gate program only
+pub const P2HOT_AIR_GATE_CONST: u32 = 5;
 pub const P2HOT_AIR_ADD: u32 = 0;
 pub const P2HOT_AIR_SUB: u32 = 1;
 pub const P2HOT_AIR_MUL: u32 = 2;
@@ -560,6 +574,25 @@ extern "C" {
         gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gate_sums: *const *const u64, num_lu_slots: c_uint, num_lut_slots: c_uint,
         num_luts: c_uint, lookup_selectors_first_col: usize, deltas: *const u64, lut_re_poly_evals: *const u64, gates: *const P2hotGateSet,
         values_out: *mut u64, chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
+    // ---- gate programs: the three entry points above plus the user-defined gates as data
+    pub fn p2hot_gate_sums_programs(
+        ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize, gates: *const P2hotGateSet,
+        quotient_degree_factor: c_uint, alphas: *const u64, num_challenges: c_uint, out_host: *mut u64, programs: *const P2hotGateProgram,
+        num_programs: c_uint,
+    ) -> c_int;
+    pub fn p2hot_quotient_polys_gate_programs(
+        ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize,
+        zs_partial_products: *const P2hotBatch, k_is: *const u64, num_routed: c_uint, quotient_degree_factor: c_uint, betas: *const u64,
+        gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gate_sums: *const *const u64, gates: *const P2hotGateSet,
+        values_out: *mut u64, chunks_out: *mut *mut P2hotCols, programs: *const P2hotGateProgram, num_programs: c_uint,
+    ) -> c_int;
+    pub fn p2hot_quotient_polys_lookup_gate_programs(
+        ctx: *mut P2hotCtx, wires: *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize,
+        zs_partial_products_lookups: *const P2hotBatch, k_is: *const u64, num_routed: c_uint, quotient_degree_factor: c_uint, betas: *const u64,
+        gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gate_sums: *const *const u64, num_lu_slots: c_uint, num_lut_slots: c_uint,
+        num_luts: c_uint, lookup_selectors_first_col: usize, deltas: *const u64, lut_re_poly_evals: *const u64, gates: *const P2hotGateSet,
+        values_out: *mut u64, chunks_out: *mut *mut P2hotCols, programs: *const P2hotGateProgram, num_programs: c_uint,
     ) -> c_int;
     // ---- batch FRI (batch_fri/{oracle,prover}.rs, hash/batch_merkle_tree.rs); not hooked into the patched crate yet
     pub fn p2hot_batch_merkle_dev(

@@ -99,6 +99,10 @@ class AirProgram(C.Structure):  # p2hot_air_program
                [(name, C.c_uint32) for name in ("num_insns", "num_constants", "num_temps", "num_publics")]
 
 
+class GateProgram(C.Structure):  # p2hot_gate_program
+    _fields_ = [(name, C.c_uint32) for name in ("row", "selector_index", "group_first", "group_end")] + [("program", AirProgram)]
+
+
 # p2hot_allgather_fn: (user, d_base, offsets, world, bytes, hip_stream) -> int
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.POINTER(sz), C.c_int, sz, vp)
 
@@ -195,6 +199,10 @@ SIGNATURES = {
     "p2hot_air_max_temps": (u, []),
     "p2hot_stark_constraint_accs": (i, [vp, vp, vp, vp, u, vp, u, vp]),
     "p2hot_stark_quotient_polys_air": (i, [vp, vp, vp, vp, vp, u, vp, vp, u, vp, u, vp, u, vp, vp, vp, C.POINTER(vp)]),
+    "p2hot_gate_sums_programs": (i, [vp, vp, vp, sz, vp, u, vp, u, vp, vp, u]),
+    "p2hot_quotient_polys_gate_programs": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), vp, vp, C.POINTER(vp), vp, u]),
+    "p2hot_quotient_polys_lookup_gate_programs": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), u, u, u, sz, vp, vp, vp,
+                                                      vp, C.POINTER(vp), vp, u]),
     "p2hot_batch_merkle_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, u, vp, vp]),
     "p2hot_batch_merkle_rows_dev": (i, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(u), sz, vp, sz, vp]),
     "p2hot_batch_merkle_paths_dev": (i, [vp, vp, C.POINTER(u), sz, u, vp, sz, vp]),

@@ -1585,11 +1585,161 @@ static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_ba
     return P2HOT_OK;
 }
 
+// ------------------------------------------------------------------ gate programs (gate_program.hpp; include/p2hot.h)
+// the checked programs of one call as one device block: public_inputs_hash, the constants, the headers, then the instructions
+struct GateProgPlan {
+    std::vector<u64> blob;  // host image of the device block (outlives the asynchronous copy)
+    size_t n_consts = 0, n_gates = 0, n_insns = 0;
+    unsigned num_temps = 0;
+    bool empty() const { return n_gates == 0; }
+};
+
+// every check of the programs, before anything is enqueued (include/p2hot.h lists them); `gs` has passed gates_validate.
+// *max_constraints grows to the longest constraint list among the programs (the alpha-power table's length)
+static int gate_programs_validate(p2hot_ctx *ctx, const p2hot_gate_program *programs, unsigned num_programs, const p2hot_gate_set *gs,
+                                  const p2hot_batch *wires, size_t sigmas_first_col, unsigned quotient_degree_factor, const char *what,
+                                  unsigned *max_constraints, GateProgPlan *pl) {
+    if (num_programs == 0) return P2HOT_OK;
+    if (!programs) P2_FAIL(ctx, P2HOT_EINVAL, "%s: %u gate programs but a null program array", what, num_programs);
+    const size_t consts_first = (size_t)gs->num_selectors + gs->num_lookup_selectors;
+    const u32 unwritten = ~0u, sat = 1u << 20;
+    std::vector<p2hot_air_insn> insns;
+    std::vector<u64> constants;
+    std::vector<gateprog::Header> headers(num_programs);
+    std::set<u32> rows;
+    for (unsigned k = 0; k < gs->num_gates; ++k) rows.insert(gs->gates[k].row);
+    for (unsigned p = 0; p < num_programs; ++p) {
+        const p2hot_gate_program &g = programs[p];
+        const p2hot_air_program &pr = g.program;
+        if ((pr.num_insns && !pr.insns) || (pr.num_constants && !pr.constants))
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: a program array is null but its count is not", what, p);
+        if (g.row < g.group_first || g.row >= g.group_end) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: row %u outside its group [%u, %u)", what, p, g.row, g.group_first, g.group_end);
+        if (g.group_end - g.group_first > 256) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: a selector group of %u gates (at most 256)", what, p, g.group_end - g.group_first);
+        if (g.selector_index >= gs->num_selectors) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: selector %u of %u", what, p, g.selector_index, gs->num_selectors);
+        if (consts_first > sigmas_first_col)  // (the selector column itself must lie in front of the sigmas)
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: %u selectors and %u lookup selectors reach past sigmas_first_col = %zu", what, p, gs->num_selectors,
+                    gs->num_lookup_selectors, sigmas_first_col);
+        if (!rows.insert(g.row).second)
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: row %u is already a gate of this call (a descriptor of the set or an earlier program)", what, p, g.row);
+        if (pr.num_publics > 4) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u names %u words of a public_inputs_hash of 4", what, p, pr.num_publics);
+        if (pr.num_temps > air::MAX_TEMPS)
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: program %u uses %u temp slots (p2hot_air_max_temps() = %u)", what, p, pr.num_temps, air::MAX_TEMPS);
+        // the filter's degree (gate.rs:326-333) on top of every constraint's; max_degree = factor + 1 (gates/selectors.rs:101-160)
+        const u32 filter_degree = g.group_end - g.group_first - 1 + (gs->num_selectors > 1 ? 1 : 0), max_degree = quotient_degree_factor + 1;
+        std::vector<u32> tdeg(pr.num_temps, unwritten);
+        unsigned ncons = 0;
+        for (u32 k = 0; k < pr.num_insns; ++k) {
+            p2hot_air_insn in = pr.insns[k];
+            if (in.op > P2HOT_AIR_CONSTRAINT_LAST_ROW) P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: program %u: instruction %u: unknown op %u", what, p, k, in.op);
+            if (in.op > P2HOT_AIR_CONSTRAINT)
+                P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: program %u: instruction %u: op %u is a STARK consumer's filtered constraint, not a gate's", what, p, k, in.op);
+            const bool arith = in.op <= P2HOT_AIR_MUL;
+            u32 deg[2] = {0, 0};
+            for (int s = 0; s < (arith ? 2 : 1); ++s) {
+                u32 &o = s ? in.b : in.a;
+                const u32 kind = o >> air::KIND_SHIFT, idx = o & air::INDEX_MASK;
+                const char side = s ? 'b' : 'a';
+                switch (kind) {
+                    case P2HOT_AIR_LOCAL:
+                        if (idx >= wires->W) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c reads wire %u of %zu", what, p, k, side, idx, wires->W);
+                        deg[s] = 1;
+                        break;
+                    case P2HOT_AIR_GATE_CONST:
+                        if (consts_first + idx >= sigmas_first_col)
+                            P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c reads gate constant %u: %u selectors, %u lookup selectors and it reach sigmas_first_col = %zu",
+                                    what, p, k, side, idx, gs->num_selectors, gs->num_lookup_selectors, sigmas_first_col);
+                        deg[s] = 1;
+                        break;
+                    case P2HOT_AIR_NEXT:
+                        P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c reads the next row, which a gate does not see", what, p, k, side);
+                    case P2HOT_AIR_PUBLIC:
+                        if (idx >= pr.num_publics) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c reads hash word %u of %u", what, p, k, side, idx, pr.num_publics);
+                        break;
+                    case P2HOT_AIR_CONST:
+                        if (idx >= pr.num_constants) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c reads constant %u of %u", what, p, k, side, idx, pr.num_constants);
+                        o = P2HOT_AIR_OPERAND(P2HOT_AIR_CONST, constants.size() + idx);  // rebased into the call's one constant array
+                        break;
+                    case P2HOT_AIR_TEMP:
+                        if (idx >= pr.num_temps) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c reads temp %u of %u", what, p, k, side, idx, pr.num_temps);
+                        if (tdeg[idx] == unwritten) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c reads temp %u before any instruction wrote it", what, p, k, side, idx);
+                        deg[s] = tdeg[idx];
+                        break;
+                    default:
+                        P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: operand %c has the unknown kind %u", what, p, k, side, kind);
+                }
+            }
+            if (arith) {
+                if (in.dst >= pr.num_temps) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u writes temp %u of %u", what, p, k, in.dst, pr.num_temps);
+                tdeg[in.dst] = std::min(sat, in.op == P2HOT_AIR_MUL ? deg[0] + deg[1] : std::max(deg[0], deg[1]));
+            } else {
+                if (deg[0] + filter_degree > max_degree)
+                    P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: instruction %u: a constraint of degree %u under a filter of degree %u, above quotient_degree_factor + 1 = %u",
+                            what, p, k, deg[0], filter_degree, max_degree);
+                ++ncons;
+            }
+            insns.push_back(in);
+        }
+        if (constants.size() + pr.num_constants > air::INDEX_MASK) P2_FAIL(ctx, P2HOT_EINVAL, "%s: program %u: the programs' constants do not fit an operand index", what, p);
+        gateprog::Header &h = headers[p];
+        h.gate = p2hot_gate{0, g.row, g.selector_index, g.group_first, g.group_end, 0, 0};
+        h.insn_first = (u32)(insns.size() - pr.num_insns), h.insn_end = (u32)insns.size(), h.pad = 0;
+        for (u32 k = 0; k < pr.num_constants; ++k) constants.push_back(gl::canon(pr.constants[k]));
+        pl->num_temps = std::max(pl->num_temps, pr.num_temps);
+        if (ncons > *max_constraints) *max_constraints = ncons;
+    }
+    pl->n_consts = constants.size(), pl->n_gates = num_programs, pl->n_insns = insns.size();
+    pl->blob.assign(4 + pl->n_consts + 5 * pl->n_gates + 2 * pl->n_insns + 1, 0);
+    for (unsigned k = 0; k < 4; ++k) pl->blob[k] = gl::canon(gs->public_inputs_hash[k]);
+    std::copy(constants.begin(), constants.end(), pl->blob.begin() + 4);
+    memcpy(pl->blob.data() + 4 + pl->n_consts, headers.data(), headers.size() * sizeof(gateprog::Header));
+    if (!insns.empty()) memcpy(pl->blob.data() + 4 + pl->n_consts + 5 * pl->n_gates, insns.data(), insns.size() * sizeof(p2hot_air_insn));
+    return P2HOT_OK;
+}
+
+// uploads the block and evaluates every program gate in one launch, adding into d_out [nc][1 << log_nq] like the gate kernels
+static int gate_programs_launch(p2hot_ctx *ctx, const GateProgPlan &pl, PoolBuf &d_blob, const p2hot_gate_set *gs, const p2hot_batch *wires,
+                                const p2hot_batch *constants_sigmas, const u64 *d_apow, unsigned apow_stride, u64 *d_out, unsigned log_nq,
+                                unsigned nc) {
+    if (pl.empty()) return P2HOT_OK;
+    P2_HIP(ctx, hipMemcpyAsync(d_blob.p, pl.blob.data(), pl.blob.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    gateprog::Args a{};
+    a.pih = d_blob.u(), a.constants = d_blob.u() + 4;
+    a.headers = (const gateprog::Header *)(d_blob.u() + 4 + pl.n_consts);
+    a.insns = (const p2hot_air_insn *)(d_blob.u() + 4 + pl.n_consts + 5 * pl.n_gates);
+    a.wires = wires->d_lde, a.wires_stride = wires->col_stride_lde();
+    a.consts = constants_sigmas->d_lde, a.consts_stride = constants_sigmas->col_stride_lde();
+    a.apow = d_apow, a.apow_stride = apow_stride, a.out = d_out, a.log_nq = log_nq, a.num_gates = (unsigned)pl.n_gates;
+    a.num_selectors = gs->num_selectors, a.consts_first = gs->num_selectors + gs->num_lookup_selectors;
+    ProfScope prof(ctx, "gate_programs");
+    const size_t shm = (size_t)(pl.num_temps ? pl.num_temps : 1) * gateprog::BLOCK * 8;
+    const dim3 grid(cdiv((size_t)1 << log_nq, gateprog::BLOCK)), block(gateprog::BLOCK);
+    switch (nc) {
+        case 1:
+            P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(gateprog::interp_kernel<1>), shm));
+            P2HOT_LAUNCH((gateprog::interp_kernel<1>), grid, block, shm, ctx->stream, a);
+            break;
+        case 2:
+            P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(gateprog::interp_kernel<2>), shm));
+            P2HOT_LAUNCH((gateprog::interp_kernel<2>), grid, block, shm, ctx->stream, a);
+            break;
+        case 3:
+            P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(gateprog::interp_kernel<3>), shm));
+            P2HOT_LAUNCH((gateprog::interp_kernel<3>), grid, block, shm, ctx->stream, a);
+            break;
+        default:
+            P2_TRY(lds_opt_in(ctx, reinterpret_cast<const void *>(gateprog::interp_kernel<4>), shm));
+            P2HOT_LAUNCH((gateprog::interp_kernel<4>), grid, block, shm, ctx->stream, a);
+            break;
+    }
+    P2_LAUNCH_CHECK(ctx);
+    return P2HOT_OK;
+}
+
 // the reduced gate sums on their own (include/p2hot.h): evaluate_gate_constraints_base_batch (plonk/vanishing_poly.rs:702-728) for
-// the gates of the set, reduced by the powers of every alpha
-extern "C" int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
-                               const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,
-                               uint64_t *out_host) {
+// the gates of the set and the program gates, reduced by the powers of every alpha
+static int gate_sums_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                          const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,
+                          uint64_t *out_host, const p2hot_gate_program *programs, unsigned num_programs) {
     P2_ENTER(ctx);
     if (!wires || !constants_sigmas || !alphas || !out_host) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: null argument");
     if (wires->ctx != ctx || constants_sigmas->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: a commitment belongs to another context");
@@ -1602,9 +1752,12 @@ extern "C" int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p
     if (qbits > wires->rate_bits) P2_FAIL(ctx, P2HOT_EINVAL, "gate_sums: quotient degree 2^%u above the rate 2^%u (prover.rs:632-636)", qbits, wires->rate_bits);
     unsigned stride = 1;
     P2_TRY(gates_validate(ctx, gates, wires, constants_sigmas, sigmas_first_col, quotient_degree_factor, "gate_sums", &stride));
+    GateProgPlan plan;
+    P2_TRY(gate_programs_validate(ctx, programs, num_programs, gates, wires, sigmas_first_col, quotient_degree_factor, "gate_sums_programs", &stride, &plan));
     const unsigned log_nq = wires->log_n + qbits;
     const size_t m = (size_t)1 << log_nq;
-    PoolBuf d_out(ctx), d_apow(ctx);
+    PoolBuf d_out(ctx), d_apow(ctx), d_prog(ctx);
+    if (!plan.empty()) P2_TRY(pool_alloc(ctx, plan.blob.size() * 8, &d_prog.p));
     P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8, &d_out.p));
     P2_TRY(pool_alloc(ctx, (size_t)num_challenges * stride * 8, &d_apow.p));
     std::vector<u64> apow((size_t)num_challenges * stride);
@@ -1613,10 +1766,24 @@ extern "C" int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p
         P2_HIP(ctx, hipMemcpyAsync(d_apow.p, apow.data(), apow.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         P2_HIP(ctx, hipMemsetAsync(d_out.p, 0, (size_t)num_challenges * m * 8, ctx->stream));
         P2_TRY(gates_launch(ctx, gates, wires, constants_sigmas, d_apow.u(), stride, d_out.u(), log_nq, num_challenges));
+        P2_TRY(gate_programs_launch(ctx, plan, d_prog, gates, wires, constants_sigmas, d_apow.u(), stride, d_out.u(), log_nq, num_challenges));
         P2_HIP(ctx, hipMemcpyAsync(out_host, d_out.p, (size_t)num_challenges * m * 8, hipMemcpyDeviceToHost, ctx->stream));
         return P2HOT_OK;
     };
     return sync_checked(ctx, body(), "gate_sums");
+}
+
+extern "C" int p2hot_gate_sums(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                               const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas, unsigned num_challenges,
+                               uint64_t *out_host) {
+    return gate_sums_core(ctx, wires, constants_sigmas, sigmas_first_col, gates, quotient_degree_factor, alphas, num_challenges, out_host, nullptr, 0);
+}
+
+extern "C" int p2hot_gate_sums_programs(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas, size_t sigmas_first_col,
+                                        const p2hot_gate_set *gates, unsigned quotient_degree_factor, const uint64_t *alphas,
+                                        unsigned num_challenges, uint64_t *out_host, const p2hot_gate_program *programs, unsigned num_programs) {
+    return gate_sums_core(ctx, wires, constants_sigmas, sigmas_first_col, gates, quotient_degree_factor, alphas, num_challenges, out_host, programs,
+                          num_programs);
 }
 
 // compute_quotient_polys (plonky2/src/plonk/prover.rs:609-815) without its gate evaluation: the permutation argument's vanishing
@@ -1634,7 +1801,8 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
                                const p2hot_batch *zs_partial_products, const uint64_t *k_is, unsigned num_routed,
                                unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
                                unsigned num_challenges, const uint64_t *const *gate_sums, uint64_t *values_out, p2hot_cols **chunks_out,
-                               const LookupQuot *lk, const p2hot_gate_set *gs = nullptr, bool with_gates = false) {
+                               const LookupQuot *lk, const p2hot_gate_set *gs = nullptr, bool with_gates = false,
+                               const p2hot_gate_program *programs = nullptr, unsigned num_programs = 0) {
     P2_ENTER(ctx);
     if (chunks_out) *chunks_out = nullptr;
     if (!wires || !constants_sigmas || !zs_partial_products || !k_is || !betas || !gammas || !alphas) P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys: null argument");
@@ -1676,10 +1844,16 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
             P2_FAIL(ctx, P2HOT_EINVAL, "quotient_polys_lookup: the lookup selectors do not fit the constants_sigmas commitment");
     }
     unsigned gs_stride = 0;
-    if (with_gates) P2_TRY(gates_validate(ctx, gs, wires, constants_sigmas, sigmas_first_col, quotient_degree_factor, "quotient_polys_gates", &gs_stride));
+    GateProgPlan plan;
+    if (with_gates) {
+        P2_TRY(gates_validate(ctx, gs, wires, constants_sigmas, sigmas_first_col, quotient_degree_factor, "quotient_polys_gates", &gs_stride));
+        P2_TRY(gate_programs_validate(ctx, programs, num_programs, gs, wires, sigmas_first_col, quotient_degree_factor, "quotient_polys_gate_programs",
+                                      &gs_stride, &plan));
+    }
     const size_t n_apow = lk ? (size_t)num_challenges * ((size_t)num_challenges * lk_Kc + 1) : 0, n_evals = lk ? (size_t)num_challenges * lk->num_luts : 0;
     const size_t n_gpow = (size_t)num_challenges * gs_stride;
-    PoolBuf d_work(ctx), d_small(ctx), d_gate(ctx);
+    PoolBuf d_work(ctx), d_small(ctx), d_gate(ctx), d_prog(ctx);
+    if (!plan.empty()) P2_TRY(pool_alloc(ctx, plan.blob.size() * 8, &d_prog.p));
     P2_TRY(pool_alloc(ctx, (size_t)num_challenges * m * 8 + 8, &d_work.p));
     const size_t nbk = (size_t)num_challenges * num_routed;
     P2_TRY(pool_alloc(ctx, (nbk + 2 * rate + n_apow + n_evals + n_gpow) * 8, &d_small.p));
@@ -1752,6 +1926,8 @@ static int quotient_polys_core(p2hot_ctx *ctx, const p2hot_batch *wires, const p
         if (with_gates) {  // on top of the caller's residual sums (or of zeros)
             if (!gate_sums) P2_HIP(ctx, hipMemsetAsync(d_gate.p, 0, (size_t)num_challenges * m * 8, ctx->stream));
             P2_TRY(gates_launch(ctx, gs, wires, constants_sigmas, d_small.u() + nbk + 2 * rate + n_apow + n_evals, gs_stride, d_gate.u(), log_nq, num_challenges));
+            P2_TRY(gate_programs_launch(ctx, plan, d_prog, gs, wires, constants_sigmas, d_small.u() + nbk + 2 * rate + n_apow + n_evals, gs_stride, d_gate.u(),
+                                        log_nq, num_challenges));
         }
         if (lk) {
             ProfScope prof(ctx, "quotient_lookup");
@@ -1827,6 +2003,31 @@ extern "C" int p2hot_quotient_polys_lookup_gates(p2hot_ctx *ctx, const p2hot_bat
     const LookupQuot lk{num_lu_slots, num_lut_slots, num_luts, lookup_selectors_first_col, deltas, lut_re_poly_evals};
     return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products_lookups, k_is, num_routed, quotient_degree_factor,
                                betas, gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, &lk, gates, true);
+}
+
+// the two entry points above with the constraints of user-defined gates as gate programs (gate_program.hpp) beside the set's gates
+extern "C" int p2hot_quotient_polys_gate_programs(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
+                                                  size_t sigmas_first_col, const p2hot_batch *zs_partial_products, const uint64_t *k_is,
+                                                  unsigned num_routed, unsigned quotient_degree_factor, const uint64_t *betas,
+                                                  const uint64_t *gammas, const uint64_t *alphas, unsigned num_challenges,
+                                                  const uint64_t *const *gate_sums, const p2hot_gate_set *gates, uint64_t *values_out,
+                                                  p2hot_cols **chunks_out, const p2hot_gate_program *programs, unsigned num_programs) {
+    return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products, k_is, num_routed, quotient_degree_factor, betas,
+                               gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, nullptr, gates, true, programs, num_programs);
+}
+
+extern "C" int p2hot_quotient_polys_lookup_gate_programs(p2hot_ctx *ctx, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
+                                                         size_t sigmas_first_col, const p2hot_batch *zs_partial_products_lookups,
+                                                         const uint64_t *k_is, unsigned num_routed, unsigned quotient_degree_factor,
+                                                         const uint64_t *betas, const uint64_t *gammas, const uint64_t *alphas,
+                                                         unsigned num_challenges, const uint64_t *const *gate_sums, unsigned num_lu_slots,
+                                                         unsigned num_lut_slots, unsigned num_luts, size_t lookup_selectors_first_col,
+                                                         const uint64_t *deltas, const uint64_t *lut_re_poly_evals, const p2hot_gate_set *gates,
+                                                         uint64_t *values_out, p2hot_cols **chunks_out, const p2hot_gate_program *programs,
+                                                         unsigned num_programs) {
+    const LookupQuot lk{num_lu_slots, num_lut_slots, num_luts, lookup_selectors_first_col, deltas, lut_re_poly_evals};
+    return quotient_polys_core(ctx, wires, constants_sigmas, sigmas_first_col, zs_partial_products_lookups, k_is, num_routed, quotient_degree_factor,
+                               betas, gammas, alphas, num_challenges, gate_sums, values_out, chunks_out, &lk, gates, true, programs, num_programs);
 }
 
 // ------------------------------------------------------------------ lookup polynomials (plonk/prover.rs:451-605)

@@ -1,5 +1,5 @@
 // p2hot.hip -- context, pass planning and the C ABI of libp2hot (see include/p2hot.h).
-// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / stark.hpp / air.hpp / gates.hpp / gates_recursion.hpp.
+// One translation unit: the kernels live in ntt.hpp / merkle.hpp / fri.hpp / plonk.hpp / lookup.hpp / stark.hpp / air.hpp / gates.hpp / gates_recursion.hpp / gate_program.hpp.
 #include "../../include/p2hot.h"
 
 #include <algorithm>
@@ -22,6 +22,7 @@
 #include "air.hpp"
 #include "gates.hpp"
 #include "gates_recursion.hpp"
+#include "gate_program.hpp"
 #include "merkle.hpp"
 #include "keccak.hpp"
 #include "ntt.hpp"

@@ -265,13 +265,22 @@ class GateSet:
         return C.cast(C.pointer(self._set), C.c_void_p)
 
 
-def gate_sums(wires_commitment, constants_sigmas_commitment, sigmas_first_col, gate_set, quotient_degree_factor, alphas, engine=None):
+def gate_sums(wires_commitment, constants_sigmas_commitment, sigmas_first_col, gate_set, quotient_degree_factor, alphas, engine=None,
+              programs=None):
     """evaluate_gate_constraints_base_batch (vanishing_poly.rs:702-728) for the gates of `gate_set` on the quotient coset, reduced
-    by the powers of every alpha -- one p2hot_gate_sums call.  Returns [num_challenges][n << qbits], natural order, canonical."""
+    by the powers of every alpha -- one p2hot_gate_sums call.  Returns [num_challenges][n << qbits], natural order, canonical.
+    `programs`: a list of gate_program.GateProgram, the user-defined gates of the circuit (one p2hot_gate_sums_programs call)."""
     eng = engine or wires_commitment.engine
     a = np.ascontiguousarray(np.asarray(alphas, dtype=np.uint64))
     qb = max(0, (quotient_degree_factor - 1).bit_length())
     out = np.zeros((len(a), (1 << wires_commitment.degree_log) << qb), dtype=np.uint64)
+    if programs is not None:
+        from .gate_program import marshal
+        parr, pn, _keep = marshal(programs)
+        eng.check(eng.lib.p2hot_gate_sums_programs(eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, gate_set.ptr,
+                                                   quotient_degree_factor, a.ctypes.data_as(C.c_void_p), len(a), out.ctypes.data_as(C.c_void_p),
+                                                   parr, pn))
+        return out
     eng.check(eng.lib.p2hot_gate_sums(eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, gate_set.ptr,
                                       quotient_degree_factor, a.ctypes.data_as(C.c_void_p), len(a), out.ctypes.data_as(C.c_void_p)))
     return out
@@ -299,9 +308,11 @@ def _host_gate_sums(gate_sums, nc, m):
 
 
 def compute_quotient_polys_gates(wires_commitment, constants_sigmas_commitment, sigmas_first_col, zs_partial_products_commitment, k_is,
-                                 quotient_degree_factor, betas, gammas, alphas, gate_set, gate_sums=None, want_values=False, engine=None):
+                                 quotient_degree_factor, betas, gammas, alphas, gate_set, gate_sums=None, want_values=False, engine=None,
+                                 programs=None):
     """compute_quotient_polys above with the gates of `gate_set` evaluated on the device (one p2hot_quotient_polys_gates call);
-    `gate_sums`, if given, is the caller's residual of the other gates and is added to the device's sums."""
+    `gate_sums`, if given, is the caller's residual of the other gates and is added to the device's sums.  `programs`: a list of
+    gate_program.GateProgram evaluated on the device beside the set (one p2hot_quotient_polys_gate_programs call)."""
     eng = engine or wires_commitment.engine
     k = np.ascontiguousarray(np.asarray(k_is, dtype=np.uint64))
     b, g, a = (np.ascontiguousarray(np.asarray(v, dtype=np.uint64)) for v in (betas, gammas, alphas))
@@ -310,6 +321,13 @@ def compute_quotient_polys_gates(wires_commitment, constants_sigmas_commitment, 
     nc = len(b)
     m = (1 << wires_commitment.degree_log) << max(0, (quotient_degree_factor - 1).bit_length())
     gs, gptrs = _host_gate_sums(gate_sums, nc, m)
+    if programs is not None:
+        from .gate_program import marshal
+        parr, pn, _keep = marshal(programs)
+        return _quotient_call(eng, lambda vals, h: eng.lib.p2hot_quotient_polys_gate_programs(
+            eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, zs_partial_products_commitment._h,
+            k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+            a.ctypes.data_as(C.c_void_p), nc, gptrs, gate_set.ptr, vals, h, parr, pn), nc, m, want_values)
     return _quotient_call(eng, lambda vals, h: eng.lib.p2hot_quotient_polys_gates(
         eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, zs_partial_products_commitment._h,
         k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
@@ -319,9 +337,10 @@ def compute_quotient_polys_gates(wires_commitment, constants_sigmas_commitment, 
 def compute_quotient_polys_lookup_gates(wires_commitment, constants_sigmas_commitment, sigmas_first_col,
                                         zs_partial_products_lookups_commitment, k_is, quotient_degree_factor, betas, gammas, alphas,
                                         num_lu_slots, num_lut_slots, lookup_selectors_first_col, deltas, lut_re_poly_evals, gate_set,
-                                        gate_sums=None, want_values=False, engine=None):
+                                        gate_sums=None, want_values=False, engine=None, programs=None):
     """compute_quotient_polys_lookup above with the gates of `gate_set` evaluated on the device (one
-    p2hot_quotient_polys_lookup_gates call); `gate_sums` is the caller's residual of the other gates."""
+    p2hot_quotient_polys_lookup_gates call); `gate_sums` is the caller's residual of the other gates.  `programs`: a list of
+    gate_program.GateProgram evaluated beside the set (one p2hot_quotient_polys_lookup_gate_programs call)."""
     eng = engine or wires_commitment.engine
     k = np.ascontiguousarray(np.asarray(k_is, dtype=np.uint64))
     b, g, a = (np.ascontiguousarray(np.asarray(v, dtype=np.uint64)) for v in (betas, gammas, alphas))
@@ -334,6 +353,14 @@ def compute_quotient_polys_lookup_gates(wires_commitment, constants_sigmas_commi
         raise ValueError("deltas must be [num_challenges][4]")
     m = (1 << wires_commitment.degree_log) << max(0, (quotient_degree_factor - 1).bit_length())
     gs, gptrs = _host_gate_sums(gate_sums, nc, m)
+    if programs is not None:
+        from .gate_program import marshal
+        parr, pn, _keep = marshal(programs)
+        return _quotient_call(eng, lambda vals, h: eng.lib.p2hot_quotient_polys_lookup_gate_programs(
+            eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, zs_partial_products_lookups_commitment._h,
+            k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+            a.ctypes.data_as(C.c_void_p), nc, gptrs, num_lu_slots, num_lut_slots, ev.shape[1], lookup_selectors_first_col,
+            d.ctypes.data_as(C.c_void_p), ev.ctypes.data_as(C.c_void_p), gate_set.ptr, vals, h, parr, pn), nc, m, want_values)
     return _quotient_call(eng, lambda vals, h: eng.lib.p2hot_quotient_polys_lookup_gates(
         eng.ctx, wires_commitment._h, constants_sigmas_commitment._h, sigmas_first_col, zs_partial_products_lookups_commitment._h,
         k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
