@@ -283,7 +283,8 @@ int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bit
  * p2hot_quotient_polys_gates, p2hot_quotient_polys_lookup_gates, p2hot_stark_lookup_polys, p2hot_stark_ctl_polys,
  * p2hot_stark_quotient_polys, p2hot_stark_constraint_accs, p2hot_stark_quotient_polys_air, p2hot_gate_sums_programs,
  * p2hot_quotient_polys_gate_programs, p2hot_quotient_polys_lookup_gate_programs, p2hot_ctx_trim, p2hot_batch_oracle_commit,
- * p2hot_batch_oracle_coeffs / _rows / _paths / _digests, p2hot_batch_prove_openings.  p2hot_batch_free / p2hot_batch_oracle_free / p2hot_cols_free may be called from any thread at any time (a
+ * p2hot_batch_oracle_coeffs / _rows / _paths / _digests, p2hot_batch_prove_openings, p2hot_partial_products_many,
+ * p2hot_commit_cols_many, p2hot_quotient_polys_gates_many, p2hot_eval_openings_many.  p2hot_batch_free / p2hot_batch_oracle_free / p2hot_cols_free may be called from any thread at any time (a
  * Drop, a finaliser): the block cache has its own lock.  Everything else -- the *_dev building blocks, p2hot_fri_commit,
  * p2hot_fri_pow, p2hot_challenger_* -- enqueues on the context's stream without a guard: the CALLER serialises those with
  * each other and with the host-pointer calls of the same context (the Rust shim holds the context behind a Mutex). */
@@ -662,6 +663,57 @@ int p2hot_quotient_polys_lookup_gates(p2hot_ctx *ctx, const p2hot_batch *wires, 
                                       unsigned num_luts, size_t lookup_selectors_first_col, const uint64_t *deltas,
                                       const uint64_t *lut_re_poly_evals, const p2hot_gate_set *gates, uint64_t *values_out,
                                       p2hot_cols **chunks_out);
+
+/* ================================================================ the middle of a proof for M witnesses of ONE circuit
+ * p2hot_commit_many and p2hot_prove_openings_many batch the two ends of M recursion-size proofs (2^12 rows: every launch costs more
+ * than its work).  The four entry points below batch what lies between them -- partial products and Zs, their commitment from
+ * device columns, the quotient with its gate constraints, its commitment, the OpeningSet -- for M witnesses of one circuit:
+ * sigmas, constants, selectors, the gate set and k_is are shared, wires, challenges and the public-inputs hash differ per proof.
+ * Inputs: any M >= 1; the handles of the proofs need not come from one p2hot_commit_many (shares of one block and separately
+ * committed batches mix freely; a per-proof device table carries base pointers, column strides, challenges and hash words to the
+ * kernels, one grid row per proof).  Outputs: where a column set comes back it is ONE set in p2hot_commit_many_dev's interleaved
+ * layout [W][M][n], column e of proof m being column e * M + m, ready for p2hot_commit_cols_many -- which inherits commit_many's
+ * power-of-two M; for any other M take the host outputs or commit proof by proof.  Every result equals M single-proof calls bit for
+ * bit (same canonical words, same order).  Everything is validated before the first enqueue (null entries, foreign contexts,
+ * proofs of different degree or rate; a per-proof message names the proof), M == 0 is P2HOT_OK with nothing done, numeric
+ * failures found on the device use one flag word per proof, and each call synchronises the host once.
+ * NOT in the M-form, left to the single-proof entry points: the host gate_sums residual, lookups and gate programs; Keccak trees in
+ * p2hot_commit_cols_many; the multi-GPU group; and p2hot_prove_openings_many still runs its proofs side by side, not batched. */
+
+/* all_wires_permutation_partial_products for M witnesses of one circuit.  wires[m]: the wires commitment of proof m (any
+ * handle of this context, e.g. from p2hot_commit_many); the routed wires' VALUES on H are recomputed on the device from its
+ * coefficients (forward NTT, as p2hot_batch_subgroup_values does), nothing is uploaded.  sigmas: ONE column set shared by
+ * all proofs.  betas / gammas HOST [M][nc].  out_host [M][rows][n] (rows = nc * (num_prods + 1), p2hot_partial_products'
+ * order) and / or out_cols: ONE set of rows * M columns in the interleaved layout.  A zero denominator in proof j is
+ * P2HOT_EINVAL and the message names j.  num_challenges 1..4; M * num_routed <= 65535. */
+int p2hot_partial_products_many(p2hot_ctx *ctx, size_t M, const p2hot_batch *const *wires, size_t wires_first_col,
+                                const p2hot_cols *sigmas, size_t sigmas_first_col, const uint64_t *k_is, unsigned num_routed,
+                                unsigned degree, const uint64_t *betas, const uint64_t *gammas, unsigned num_challenges,
+                                uint64_t *out_host, p2hot_cols **out_cols);
+
+/* p2hot_commit_cols for an interleaved set of W * M columns: p2hot_commit_many_dev on the set's block, M handles out
+ * (shared blocks, freed with the last handle, as p2hot_commit_many's).  Poseidon trees; M a power of two, W * M <= 65535
+ * (commit_many's limits, same messages).  Consumes `cols` under exactly p2hot_commit_cols' ownership rule: P2HOT_EINVAL and
+ * P2HOT_EBUSY mean "not consumed", as does M == 0.  caps_out [M][2^cap_height][4], optional. */
+int p2hot_commit_cols_many(p2hot_ctx *ctx, p2hot_cols *cols, size_t M, unsigned rate_bits, unsigned cap_height, int is_values,
+                           uint64_t *caps_out, p2hot_batch **handles_out);
+
+/* p2hot_quotient_polys_gates for M witnesses of one circuit: wires[m] / zs_partial_products[m] per proof, constants_sigmas
+ * and the gate set shared; betas / gammas / alphas HOST [M][nc]; public_inputs_hashes HOST [M][4] (replaces the set's own
+ * field per proof; NULL = the set's for all).  gates = NULL: permutation terms only.  values_out HOST [M][nc][n << qbits];
+ * chunks_out: ONE set of nc * quotient_degree_factor * M columns, interleaved, ready for p2hot_commit_cols_many(is_values = 0).
+ * "Quotient has failed ..." names the first proof whose tail is not zero. */
+int p2hot_quotient_polys_gates_many(p2hot_ctx *ctx, size_t M, const p2hot_batch *const *wires, const p2hot_batch *constants_sigmas,
+                                    size_t sigmas_first_col, const p2hot_batch *const *zs_partial_products, const uint64_t *k_is,
+                                    unsigned num_routed, unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas,
+                                    const uint64_t *alphas, unsigned num_challenges, const p2hot_gate_set *gates,
+                                    const uint64_t *public_inputs_hashes, uint64_t *values_out, p2hot_cols **chunks_out);
+
+/* p2hot_eval_openings for M proofs: proof j evaluates batches[j * n_batches .. + n_batches) at points[j] ([n_points][2]);
+ * the same handle may appear for several j (the shared constants_sigmas).  out: proof j's block in p2hot_eval_openings'
+ * layout, the M blocks back to back. */
+int p2hot_eval_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_batch *const *batches, size_t n_batches,
+                             const uint64_t *points, size_t n_points, uint64_t *out);
 
 /* ================================================================ starky: logUp lookups and cross-table lookups of one STARK table
  * The stage of starky/src/prover.rs::prove_with_commitment between the trace commitment and the quotient commitment.  Poseidon

@@ -594,6 +594,26 @@ extern "C" {
         num_luts: c_uint, lookup_selectors_first_col: usize, deltas: *const u64, lut_re_poly_evals: *const u64, gates: *const P2hotGateSet,
         values_out: *mut u64, chunks_out: *mut *mut P2hotCols, programs: *const P2hotGateProgram, num_programs: c_uint,
     ) -> c_int;
+    // ---- the middle of a proof for M witnesses of one circuit (declarations only: the aggregator that would call them is not part of
+    // the patched crate; include/p2hot.h has the contract)
+    pub fn p2hot_partial_products_many(
+        ctx: *mut P2hotCtx, M: usize, wires: *const *const P2hotBatch, wires_first_col: usize, sigmas: *const P2hotCols, sigmas_first_col: usize,
+        k_is: *const u64, num_routed: c_uint, degree: c_uint, betas: *const u64, gammas: *const u64, num_challenges: c_uint,
+        out_host: *mut u64, out_cols: *mut *mut P2hotCols,
+    ) -> c_int;
+    pub fn p2hot_commit_cols_many(
+        ctx: *mut P2hotCtx, cols: *mut P2hotCols, M: usize, rate_bits: c_uint, cap_height: c_uint, is_values: c_int, caps_out: *mut u64,
+        handles_out: *mut *mut P2hotBatch,
+    ) -> c_int;
+    pub fn p2hot_quotient_polys_gates_many(
+        ctx: *mut P2hotCtx, M: usize, wires: *const *const P2hotBatch, constants_sigmas: *const P2hotBatch, sigmas_first_col: usize,
+        zs_partial_products: *const *const P2hotBatch, k_is: *const u64, num_routed: c_uint, quotient_degree_factor: c_uint, betas: *const u64,
+        gammas: *const u64, alphas: *const u64, num_challenges: c_uint, gates: *const P2hotGateSet, public_inputs_hashes: *const u64,
+        values_out: *mut u64, chunks_out: *mut *mut P2hotCols,
+    ) -> c_int;
+    pub fn p2hot_eval_openings_many(
+        ctx: *mut P2hotCtx, M: usize, batches: *const *const P2hotBatch, n_batches: usize, points: *const u64, n_points: usize, out: *mut u64,
+    ) -> c_int;
     // ---- batch FRI (batch_fri/{oracle,prover}.rs, hash/batch_merkle_tree.rs); not hooked into the patched crate yet
     pub fn p2hot_batch_merkle_dev(
         ctx: *mut P2hotCtx, d_groups: *const *const u64, strides: *const usize, widths: *const usize, log_heights: *const c_uint,

@@ -193,6 +193,10 @@ SIGNATURES = {
     "p2hot_quotient_polys_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), vp, vp, C.POINTER(vp)]),
     "p2hot_quotient_polys_lookup_gates": (i, [vp, vp, vp, sz, vp, vp, u, u, vp, vp, vp, u, C.POINTER(vp), u, u, u, sz, vp, vp, vp, vp,
                                               C.POINTER(vp)]),
+    "p2hot_partial_products_many": (i, [vp, sz, C.POINTER(vp), sz, vp, sz, vp, u, u, vp, vp, u, vp, C.POINTER(vp)]),
+    "p2hot_commit_cols_many": (i, [vp, vp, sz, u, u, i, vp, C.POINTER(vp)]),
+    "p2hot_quotient_polys_gates_many": (i, [vp, sz, C.POINTER(vp), vp, sz, C.POINTER(vp), vp, u, u, vp, vp, vp, u, vp, vp, vp, C.POINTER(vp)]),
+    "p2hot_eval_openings_many": (i, [vp, sz, C.POINTER(vp), sz, vp, sz, vp]),
     "p2hot_stark_lookup_polys": (i, [vp, vp, vp, vp, u, vp, u, u, vp, C.POINTER(vp)]),
     "p2hot_stark_ctl_polys": (i, [vp, vp, vp, vp, u, u, vp, C.POINTER(vp), vp]),
     "p2hot_stark_quotient_polys": (i, [vp, vp, vp, vp, vp, u, vp, vp, u, vp, u, vp, u, C.POINTER(vp), vp, C.POINTER(vp)]),

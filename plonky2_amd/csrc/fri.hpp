@@ -397,7 +397,7 @@ __global__ void query_indices_kernel(const u64 *rand, size_t n_queries, unsigned
 }
 
 // w0[u] + X w1[u] = z^u for u < count (the power table of one segment, shared by every segment of every polynomial)
-__global__ void ext_powers_kernel(gl::ext2 z, unsigned count, u64 *w0, u64 *w1) {
+__device__ __forceinline__ void ext_powers_body(gl::ext2 z, unsigned count, u64 *w0, u64 *w1) {
     const unsigned u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= count) return;
     gl::ext2 w{1, 0}, b = z;
@@ -408,12 +408,17 @@ __global__ void ext_powers_kernel(gl::ext2 z, unsigned count, u64 *w0, u64 *w1) 
     w0[u] = w.a0;
     w1[u] = w.a1;
 }
+__global__ void ext_powers_kernel(gl::ext2 z, unsigned count, u64 *w0, u64 *w1) { ext_powers_body(z, count, w0, w1); }
+// one table per point of a point list (grid row y): pts [G][2] canonical, w [G][2][count]
+__global__ void ext_powers_many_kernel(const u64 *__restrict__ pts, unsigned count, u64 *w) {
+    u64 *w0 = w + (size_t)blockIdx.y * 2 * count;
+    ext_powers_body(gl::ext2{pts[2 * blockIdx.y], pts[2 * blockIdx.y + 1]}, count, w0, w0 + count);
+}
 
 // Stage 1 as a dot product with the segment's power table: the coefficients are base-field elements, so a term is two
 // base multiplications instead of the extension multiplication of a Horner step (about 40 instructions instead of 110).
-__global__ void __launch_bounds__(256) eval_polys_dot_kernel(const u64 *const *polys, unsigned seg_log, const u64 *w0,
-                                                            const u64 *w1, u64 *part /* [J][S][2] */) {
-    __shared__ u64 s0[256], s1[256];
+__device__ __forceinline__ void eval_polys_dot_body(const u64 *const *polys, unsigned seg_log, const u64 *w0, const u64 *w1, u64 *part, u64 *s0,
+                                                    u64 *s1) {
     const unsigned tid = threadIdx.x;
     const size_t seg = (size_t)1 << seg_log;
     const u64 *c = polys[blockIdx.x] + (size_t)blockIdx.y * seg;
@@ -439,10 +444,22 @@ __global__ void __launch_bounds__(256) eval_polys_dot_kernel(const u64 *const *p
         o[1] = s1[0];
     }
 }
-
-__global__ void __launch_bounds__(256) eval_polys_stage2_kernel(const u64 *part, size_t n_seg, gl::ext2 zs, gl::ext2 zs256,
-                                                               u64 *out /* [J][2] */) {
+__global__ void __launch_bounds__(256) eval_polys_dot_kernel(const u64 *const *polys, unsigned seg_log, const u64 *w0,
+                                                            const u64 *w1, u64 *part /* [J][S][2] */) {
     __shared__ u64 s0[256], s1[256];
+    eval_polys_dot_body(polys, seg_log, w0, w1, part, s0, s1);
+}
+// A point set per polynomial range (p2hot_eval_openings_many): polynomial j belongs to group grp[j] (a proof) and is evaluated at
+// that group's P = gridDim.z points; point z of group g has the power table w[(g * P + z)] ([2][seg] words).  part [P][J][S][2]
+__global__ void __launch_bounds__(256) eval_polys_dot_many_kernel(const u64 *const *polys, const unsigned *__restrict__ grp, unsigned seg_log,
+                                                                 const u64 *w, u64 *part) {
+    __shared__ u64 s0[256], s1[256];
+    const size_t seg = (size_t)1 << seg_log;
+    const u64 *w0 = w + ((size_t)grp[blockIdx.x] * gridDim.z + blockIdx.z) * 2 * seg;
+    eval_polys_dot_body(polys, seg_log, w0, w0 + seg, part + 2 * (size_t)blockIdx.z * gridDim.x * gridDim.y, s0, s1);
+}
+
+__device__ __forceinline__ void eval_polys_stage2_body(const u64 *part, size_t n_seg, gl::ext2 zs, gl::ext2 zs256, u64 *out, u64 *s0, u64 *s1) {
     const unsigned tid = threadIdx.x;
     const u64 *c = part + 2 * (size_t)blockIdx.x * n_seg;
     gl::ext2 acc{0, 0};
@@ -460,6 +477,19 @@ __global__ void __launch_bounds__(256) eval_polys_stage2_kernel(const u64 *part,
         out[2 * blockIdx.x] = gl::canon(r.a0);
         out[2 * blockIdx.x + 1] = gl::canon(r.a1);
     }
+}
+__global__ void __launch_bounds__(256) eval_polys_stage2_kernel(const u64 *part, size_t n_seg, gl::ext2 zs, gl::ext2 zs256,
+                                                               u64 *out /* [J][2] */) {
+    __shared__ u64 s0[256], s1[256];
+    eval_polys_stage2_body(part, n_seg, zs, zs256, out, s0, s1);
+}
+// grid (J, P): zsp [G * P][4] = (z^seg, (z^seg)^256) per point of every group, canonical; out [P][J][2]
+__global__ void __launch_bounds__(256) eval_polys_stage2_many_kernel(const u64 *part, const unsigned *__restrict__ grp, size_t n_seg,
+                                                                    const u64 *__restrict__ zsp, u64 *out) {
+    __shared__ u64 s0[256], s1[256];
+    const u64 *z = zsp + 4 * ((size_t)grp[blockIdx.x] * gridDim.y + blockIdx.y);
+    const size_t pj = (size_t)blockIdx.y * gridDim.x;
+    eval_polys_stage2_body(part + 2 * pj * n_seg, n_seg, gl::ext2{z[0], z[1]}, gl::ext2{z[2], z[3]}, out + 2 * pj, s0, s1);
 }
 
 // merkle_tree_prove (hash/merkle_tree.rs:151-190) for m leaf indices straight from the device-resident

@@ -75,83 +75,48 @@ struct Args {
 
 template <int NC>
 __global__ void __launch_bounds__(256) cheap_gates_kernel(Args q) {
-    const size_t L = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = (size_t)1 << q.log_nq;
-    if (L >= nq) return;
-    const size_t i = q.log_nq ? (size_t)(__brevll((unsigned long long)L) >> (64 - q.log_nq)) : 0;
-    const u64 *w = q.wires + L, *lc = q.consts + (size_t)q.consts_first * q.consts_stride + L;
-    u64 res[NC];
-#pragma unroll
-    for (int a = 0; a < NC; ++a) res[a] = 0;
-    for (unsigned gi = 0; gi < q.num_gates; ++gi) {
-        const p2hot_gate &g = q.gates[gi];
-        u64 acc[NC];
-#pragma unroll
-        for (int a = 0; a < NC; ++a) acc[a] = 0;
-        auto put = [&](unsigned j, u64 term) {  // constraint j of this gate
-#pragma unroll
-            for (int a = 0; a < NC; ++a) acc[a] = gl::mul_add(term, q.apow[(size_t)a * q.apow_stride + j], acc[a]);
-        };
-        switch (g.kind) {
-            case P2HOT_GATE_CONSTANT:  // constant.rs:126-128
-                for (unsigned k = 0; k < g.param0; ++k) put(k, gl::sub(lc[(size_t)k * q.consts_stride], w[(size_t)k * q.wires_stride]));
-                break;
-            case P2HOT_GATE_PUBLIC_INPUT:  // public_input.rs:108-112
-                for (unsigned k = 0; k < 4; ++k) put(k, gl::sub(w[(size_t)k * q.wires_stride], q.pih[k]));
-                break;
-            case P2HOT_GATE_ARITHMETIC: {  // arithmetic_base.rs:173-184
-                const u64 c0 = lc[0], c1 = lc[q.consts_stride];
-                for (unsigned k = 0; k < g.param0; ++k) {
-                    const u64 *v = w + (size_t)(4 * k) * q.wires_stride;
-                    const u64 m0 = v[0], m1 = v[q.wires_stride], ad = v[2 * q.wires_stride], ou = v[3 * q.wires_stride];
-                    put(k, gl::sub(ou, gl::mul_add(gl::mul(m0, m1), c0, gl::mul(ad, c1))));
-                }
-                break;
-            }
-            case P2HOT_GATE_ARITHMETIC_EXT:  // arithmetic_extension.rs:92-110
-            case P2HOT_GATE_MUL_EXT: {       // multiplication_extension.rs:86-101
-                const bool arith = g.kind == P2HOT_GATE_ARITHMETIC_EXT;
-                const unsigned per = arith ? 8 : 6;
-                const u64 c0 = lc[0], c1 = arith ? lc[q.consts_stride] : 0;
-                for (unsigned k = 0; k < g.param0; ++k) {
-                    const u64 *v = w + (size_t)(per * k) * q.wires_stride;
-                    const gl::ext2 m0{v[0], v[q.wires_stride]}, m1{v[2 * q.wires_stride], v[3 * q.wires_stride]};
-                    const gl::ext2 pr = gl::ext_mul(m0, m1);
-                    u64 r0 = gl::mul(pr.a0, c0), r1 = gl::mul(pr.a1, c0);
-                    if (arith) {
-                        r0 = gl::mul_add(v[4 * q.wires_stride], c1, r0);
-                        r1 = gl::mul_add(v[5 * q.wires_stride], c1, r1);
-                    }
-                    const u64 *o = v + (size_t)(per - 2) * q.wires_stride;
-                    put(2 * k, gl::sub(o[0], r0));
-                    put(2 * k + 1, gl::sub(o[q.wires_stride], r1));
-                }
-                break;
-            }
-            case P2HOT_GATE_BASE_SUM: {  // base_sum.rs:153-170: limbs on wires 1 .., little endian
-                u64 sum = 0, pw = 1;
-                for (unsigned k = 0; k < g.param0; ++k) {
-                    const u64 limb = w[(size_t)(1 + k) * q.wires_stride];
-                    sum = gl::mul_add(limb, pw, sum);
-                    pw = gl::mul(pw, (u64)g.param1);
-                    u64 range = limb;
-                    for (u32 t = 1; t < g.param1; ++t) range = gl::mul(range, gl::sub(limb, (u64)t));
-                    put(1 + k, range);
-                }
-                put(0, gl::sub(sum, w[0]));
-                break;
-            }
-            default: break;  // Noop (noop.rs): no constraints
-        }
-        const u64 f = filter(g, q.consts[(size_t)g.selector_index * q.consts_stride + L], q.num_selectors > 1);
-#pragma unroll
-        for (int a = 0; a < NC; ++a) res[a] = gl::mul_add(f, acc[a], res[a]);
-    }
-#pragma unroll
-    for (int a = 0; a < NC; ++a) {
-        u64 *o = q.out + (size_t)a * nq + i;
-        *o = gl::canon(gl::add(*o, res[a]));
-    }
+#include "kbody_cheap_gates.hpp"
+}
+
+// ------------------------------------------------------------------ M witnesses of one circuit (p2hot_quotient_polys_gates_many)
+// The gate set, the constants and the selectors are shared; the wires, the alpha powers, the public-inputs hash and the output
+// differ per proof.  An M-form kernel takes the single-proof arguments plus a table with one entry per proof, runs grid row
+// blockIdx.y for proof y and reads the per-proof fields from table[y] (wave-uniform index, read-only table: scalar loads).  The
+// views below carry the member names of the argument structs, so both forms #include one body (the kbody_*.hpp fragments; the
+// single-proof kernels keep their tokens and with them their code); the alpha powers and the output of proof y lie
+// NC * apow_stride / NC * Nq words behind proof 0's.
+// (A pointer read from the table would have no known address space and cost flat loads: the table holds the proof's OFFSET from
+// proof 0's matrix, which is a kernel argument.  The views bind the shared fields by reference, so they stay kernel-argument loads;
+// the 32-bit stride keeps recursion_gates_many_kernel<4> within the scalar registers -- the host refuses a longer one.)
+struct ManyGate {
+    ptrdiff_t wires_off;    // this proof's wires LDE matrix, in words from proof 0's
+    unsigned wires_stride;  // words between its columns
+    unsigned pad_;
+    const u64 *wires;       // the same matrix and stride as a pointer and 64 bits, for the one-descriptor kernels (ManyPoseidonView)
+    size_t wires_stride64;
+    u64 pih[4];             // public_inputs_hash (canonical)
+};
+template <int NC, class A>
+struct ManyView {
+    const u64 *wires;
+    const u64 *const &consts;
+    const unsigned &wires_stride;
+    const size_t &consts_stride;
+    const u64 *apow;
+    u64 *out;
+    const unsigned &log_nq, &num_gates, &num_selectors, &consts_first, &apow_stride;
+    const u64 *pih;
+    const p2hot_gate *gates;
+    __device__ ManyView(const A &a, const ManyGate *__restrict__ tab)
+        : wires(a.wires + tab[blockIdx.y].wires_off), consts(a.consts), wires_stride(tab[blockIdx.y].wires_stride), consts_stride(a.consts_stride),
+          apow(a.apow + (size_t)blockIdx.y * NC * a.apow_stride), out(a.out + (((size_t)blockIdx.y * NC) << a.log_nq)), log_nq(a.log_nq),
+          num_gates(a.num_gates), num_selectors(a.num_selectors), consts_first(a.consts_first), apow_stride(a.apow_stride),
+          pih(tab[blockIdx.y].pih), gates(a.gates) {}
+};
+template <int NC>
+__global__ void __launch_bounds__(256) cheap_gates_many_kernel(Args shared, const ManyGate *__restrict__ tab) {
+    const ManyView<NC, Args> q(shared, tab);
+#include "kbody_cheap_gates.hpp"
 }
 
 struct PoseidonArgs {
@@ -170,107 +135,30 @@ struct PoseidonArgs {
 // dense passes of poseidon::partial_rounds4 meet other intermediate values.  Full rounds: poseidon.hpp's S-box and MDS layers.
 template <int NC>
 __global__ void __launch_bounds__(256) poseidon_gate_kernel(PoseidonArgs q) {
-    const size_t L = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = (size_t)1 << q.log_nq;
-    if (L >= nq) return;
-    const size_t i = q.log_nq ? (size_t)(__brevll((unsigned long long)L) >> (64 - q.log_nq)) : 0;
-    const u64 *w = q.wires + L;
-    auto wire = [&](unsigned c) { return w[(size_t)c * q.wires_stride]; };
-    u64 res[NC];
-#pragma unroll
-    for (int a = 0; a < NC; ++a) res[a] = 0;
-    unsigned j = 0;
-    auto put = [&](u64 term) {  // the next constraint
-#pragma unroll
-        for (int a = 0; a < NC; ++a) res[a] = gl::mul_add(term, q.apow[(size_t)a * q.apow_stride + j], res[a]);
-        ++j;
-    };
-    u64 s[12];
-    {
-        const u64 swap = wire(24);
-        put(gl::mul(swap, gl::sub(swap, 1)));
-        u64 d[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const u64 lhs = wire(k), rhs = wire(k + 4);
-            d[k] = wire(25 + k);
-            put(gl::sub(gl::mul(swap, gl::sub(rhs, lhs)), d[k]));
-            s[k] = gl::add(lhs, d[k]);
-            s[k + 4] = gl::sub(rhs, d[k]);
-        }
-#pragma unroll
-        for (int k = 8; k < 12; ++k) s[k] = wire(k);
-    }
-    // first full rounds: round 0's S-box inputs are not wires
-#pragma unroll 1
-    for (unsigned r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) s[k] = gl::add_canon(s[k], P2_POSEIDON_ALL_ROUND_CONSTANTS[12 * r + k]);
-        if (r != 0) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) {
-                const u64 x = wire(29 + 12 * (r - 1) + k);
-                put(gl::sub(s[k], x));
-                s[k] = x;
-            }
-        }
-        poseidon::sbox_layer(s);
-        poseidon::mds_layer(s, nullptr);
-    }
-    // partial_first_constant_layer, mds_partial_layer_init: result[c] = sum_{r >= 1} state[r] M[r - 1][c - 1], result[0] = state[0]
-    {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) s[k] = gl::add_canon(s[k], P2_POSEIDON_FAST_PARTIAL_FIRST_ROUND_CONSTANT[k]);
-        u64 t[12];
-#pragma unroll
-        for (int c = 1; c < 12; ++c) t[c] = gl::mul(s[1], P2_POSEIDON_FAST_PARTIAL_ROUND_INITIAL_MATRIX[c - 1]);
-#pragma unroll 1
-        for (unsigned r = 2; r < 12; ++r) {
-            u64 sr = s[2];  // s[r] by a rolled rotation of words 2..11: the state stays in registers
-#pragma unroll
-            for (int k = 2; k < 11; ++k) s[k] = s[k + 1];
-            s[11] = sr;
-#pragma unroll
-            for (int c = 1; c < 12; ++c) t[c] = gl::mul_add(sr, P2_POSEIDON_FAST_PARTIAL_ROUND_INITIAL_MATRIX[11 * (r - 1) + c - 1], t[c]);
-        }
-#pragma unroll
-        for (int c = 1; c < 12; ++c) s[c] = t[c];
-    }
-#pragma unroll 1
-    for (unsigned r = 0; r < 22; ++r) {
-        const u64 x = wire(65 + r);
-        put(gl::sub(s[0], x));
-        u64 s0 = poseidon::sbox7(x);
-        if (r != 21) s0 = gl::add_canon(s0, P2_POSEIDON_FAST_PARTIAL_ROUND_CONSTANTS[r]);
-        // mds_partial_layer_fast(r): d = s0 (M_00 = circ[0] + diag[0]) + sum_i state[i] w_hat[r][i - 1]; state[i] += s0 v[r][i - 1]
-        u64 d = gl::mul(s0, P2_POSEIDON_MDS_CIRC[0] + P2_POSEIDON_MDS_DIAG[0]);
-#pragma unroll
-        for (int k = 1; k < 12; ++k) {
-            d = gl::mul_add(s[k], P2_POSEIDON_FAST_PARTIAL_ROUND_W_HATS[11 * r + k - 1], d);
-            s[k] = gl::mul_add(s0, P2_POSEIDON_FAST_PARTIAL_ROUND_VS[11 * r + k - 1], s[k]);
-        }
-        s[0] = d;
-    }
-    // second full rounds: round_ctr = 4 + 22 + r
-#pragma unroll 1
-    for (unsigned r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const u64 x = wire(87 + 12 * r + k);
-            put(gl::sub(gl::add_canon(s[k], P2_POSEIDON_ALL_ROUND_CONSTANTS[12 * (26 + r) + k]), x));
-            s[k] = x;
-        }
-        poseidon::sbox_layer(s);
-        poseidon::mds_layer(s, nullptr);
-    }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) put(gl::sub(s[k], wire(12 + k)));
-    const u64 f = filter(q.gate, q.consts[(size_t)q.gate.selector_index * q.consts_stride + L], q.num_selectors > 1);
-#pragma unroll
-    for (int a = 0; a < NC; ++a) {
-        u64 *o = q.out + (size_t)a * nq + i;
-        *o = gl::canon(gl::mul_add(f, res[a], *o));
-    }
+#include "kbody_poseidon_gate.hpp"
+}
+// PoseidonArgs for proof blockIdx.y of M (the one-descriptor kernels: PoseidonGate here, PoseidonMdsGate in gates_recursion.hpp)
+// (poseidon_gate_kernel fills the scalar registers -- 104 of them, most as column bases of its global loads -- and every form of
+// the per-proof fields that keeps those loads global spills a few.  Here the matrix comes as the table's POINTER: the loads through
+// it are flat loads, which take their whole address from vector registers, and nothing is spilled; tests/test_many_middle_codeobj.py
+// and tests/test_gates_codeobj.py hold that.)
+template <int NC>
+struct ManyPoseidonView {
+    const u64 *wires, *consts;
+    size_t wires_stride, consts_stride;
+    const u64 *apow;
+    u64 *out;
+    unsigned log_nq, num_selectors, apow_stride;
+    const p2hot_gate &gate;
+    __device__ ManyPoseidonView(const PoseidonArgs &a, const ManyGate *__restrict__ tab)
+        : wires(tab[blockIdx.y].wires), consts(a.consts), wires_stride(tab[blockIdx.y].wires_stride64), consts_stride(a.consts_stride),
+          apow(a.apow + (size_t)blockIdx.y * NC * a.apow_stride), out(a.out + (((size_t)blockIdx.y * NC) << a.log_nq)), log_nq(a.log_nq),
+          num_selectors(a.num_selectors), apow_stride(a.apow_stride), gate(a.gate) {}
+};
+template <int NC>
+__global__ void __launch_bounds__(256) poseidon_gate_many_kernel(PoseidonArgs shared, const ManyGate *__restrict__ tab) {
+    const ManyPoseidonView<NC> q(shared, tab);
+#include "kbody_poseidon_gate.hpp"
 }
 
 }  // namespace gates

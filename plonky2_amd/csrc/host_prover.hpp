@@ -1491,11 +1491,31 @@ static void gates_alpha_powers(u64 *apow, const uint64_t *alphas, unsigned nc, u
 }
 
 // the launches: the cheap kinds MAX_CHEAP descriptors at a time, the recursion kinds the same way, then one launch per PoseidonMdsGate
-// and per PoseidonGate; all add into d_out [nc][1 << log_nq]
+// and per PoseidonGate; all add into d_out [nc][1 << log_nq].  d_many (p2hot_quotient_polys_gates_many): the M-form kernels, one grid
+// row per proof, with d_apow [M][nc][apow_stride], d_out [M][nc][1 << log_nq] and the wires and public-inputs hash of proof y in d_many[y]
+#define P2_GATES_LAUNCH(name, args)                                                                                     \
+    do {                                                                                                                \
+        if (d_many) {                                                                                                   \
+            switch (nc) {                                                                                               \
+                case 1: P2HOT_LAUNCH((gates::name##_many_kernel<1>), grid, block, 0, ctx->stream, args, d_many); break;  \
+                case 2: P2HOT_LAUNCH((gates::name##_many_kernel<2>), grid, block, 0, ctx->stream, args, d_many); break;  \
+                case 3: P2HOT_LAUNCH((gates::name##_many_kernel<3>), grid, block, 0, ctx->stream, args, d_many); break;  \
+                default: P2HOT_LAUNCH((gates::name##_many_kernel<4>), grid, block, 0, ctx->stream, args, d_many); break; \
+            }                                                                                                           \
+        } else {                                                                                                        \
+            switch (nc) {                                                                                               \
+                case 1: P2HOT_LAUNCH((gates::name##_kernel<1>), grid, block, 0, ctx->stream, args); break;               \
+                case 2: P2HOT_LAUNCH((gates::name##_kernel<2>), grid, block, 0, ctx->stream, args); break;               \
+                case 3: P2HOT_LAUNCH((gates::name##_kernel<3>), grid, block, 0, ctx->stream, args); break;               \
+                default: P2HOT_LAUNCH((gates::name##_kernel<4>), grid, block, 0, ctx->stream, args); break;              \
+            }                                                                                                           \
+        }                                                                                                               \
+    } while (0)
 static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_batch *wires, const p2hot_batch *constants_sigmas,
-                        const u64 *d_apow, unsigned apow_stride, u64 *d_out, unsigned log_nq, unsigned nc) {
+                        const u64 *d_apow, unsigned apow_stride, u64 *d_out, unsigned log_nq, unsigned nc,
+                        const gates::ManyGate *d_many = nullptr, size_t M = 1) {
     const size_t m = (size_t)1 << log_nq;
-    const dim3 grid(cdiv(m, 256)), block(256);
+    const dim3 grid(cdiv(m, 256), (unsigned)M), block(256);
     gates::Args a{};
     a.wires = wires->d_lde, a.wires_stride = wires->col_stride_lde();
     a.consts = constants_sigmas->d_lde, a.consts_stride = constants_sigmas->col_stride_lde();
@@ -1505,12 +1525,7 @@ static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_ba
     auto flush = [&]() -> int {
         if (!a.num_gates) return P2HOT_OK;
         ProfScope prof(ctx, "gates_cheap");
-        switch (nc) {
-            case 1: P2HOT_LAUNCH((gates::cheap_gates_kernel<1>), grid, block, 0, ctx->stream, a); break;
-            case 2: P2HOT_LAUNCH((gates::cheap_gates_kernel<2>), grid, block, 0, ctx->stream, a); break;
-            case 3: P2HOT_LAUNCH((gates::cheap_gates_kernel<3>), grid, block, 0, ctx->stream, a); break;
-            default: P2HOT_LAUNCH((gates::cheap_gates_kernel<4>), grid, block, 0, ctx->stream, a); break;
-        }
+        P2_GATES_LAUNCH(cheap_gates, a);
         P2_LAUNCH_CHECK(ctx);
         a.num_gates = 0;
         return P2HOT_OK;
@@ -1534,12 +1549,7 @@ static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_ba
         auto flush_rec = [&]() -> int {
             if (!ra.num_gates) return P2HOT_OK;
             ProfScope prof(ctx, "gates_recursion");
-            switch (nc) {
-                case 1: P2HOT_LAUNCH((gates::recursion_gates_kernel<1>), grid, block, 0, ctx->stream, ra); break;
-                case 2: P2HOT_LAUNCH((gates::recursion_gates_kernel<2>), grid, block, 0, ctx->stream, ra); break;
-                case 3: P2HOT_LAUNCH((gates::recursion_gates_kernel<3>), grid, block, 0, ctx->stream, ra); break;
-                default: P2HOT_LAUNCH((gates::recursion_gates_kernel<4>), grid, block, 0, ctx->stream, ra); break;
-            }
+            P2_GATES_LAUNCH(recursion_gates, ra);
             P2_LAUNCH_CHECK(ctx);
             ra.num_gates = 0;
             return P2HOT_OK;
@@ -1559,12 +1569,7 @@ static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_ba
         pa.apow = d_apow, pa.apow_stride = apow_stride, pa.out = d_out, pa.log_nq = log_nq, pa.num_selectors = gs->num_selectors;
         pa.gate = gs->gates[k];
         ProfScope prof(ctx, "gates_poseidon_mds");
-        switch (nc) {
-            case 1: P2HOT_LAUNCH((gates::mds_gate_kernel<1>), grid, block, 0, ctx->stream, pa); break;
-            case 2: P2HOT_LAUNCH((gates::mds_gate_kernel<2>), grid, block, 0, ctx->stream, pa); break;
-            case 3: P2HOT_LAUNCH((gates::mds_gate_kernel<3>), grid, block, 0, ctx->stream, pa); break;
-            default: P2HOT_LAUNCH((gates::mds_gate_kernel<4>), grid, block, 0, ctx->stream, pa); break;
-        }
+        P2_GATES_LAUNCH(mds_gate, pa);
         P2_LAUNCH_CHECK(ctx);
     }
     for (unsigned k = 0; k < gs->num_gates; ++k) {
@@ -1574,12 +1579,7 @@ static int gates_launch(p2hot_ctx *ctx, const p2hot_gate_set *gs, const p2hot_ba
         pa.apow = d_apow, pa.apow_stride = apow_stride, pa.out = d_out, pa.log_nq = log_nq, pa.num_selectors = gs->num_selectors;
         pa.gate = gs->gates[k];
         ProfScope prof(ctx, "gates_poseidon");
-        switch (nc) {
-            case 1: P2HOT_LAUNCH((gates::poseidon_gate_kernel<1>), grid, block, 0, ctx->stream, pa); break;
-            case 2: P2HOT_LAUNCH((gates::poseidon_gate_kernel<2>), grid, block, 0, ctx->stream, pa); break;
-            case 3: P2HOT_LAUNCH((gates::poseidon_gate_kernel<3>), grid, block, 0, ctx->stream, pa); break;
-            default: P2HOT_LAUNCH((gates::poseidon_gate_kernel<4>), grid, block, 0, ctx->stream, pa); break;
-        }
+        P2_GATES_LAUNCH(poseidon_gate, pa);
         P2_LAUNCH_CHECK(ctx);
     }
     return P2HOT_OK;
@@ -2122,5 +2122,421 @@ extern "C" int p2hot_cols_concat(p2hot_ctx *ctx, const p2hot_cols *a, const p2ho
     P2_TRY(sync_checked(ctx, body(), "cols_concat"));
     *out = new p2hot_cols{ctx, d.u(), a->W + b->W, a->log_n, true};
     d.p = nullptr;
+    return P2HOT_OK;
+}
+
+// ------------------------------------------------------------------ the middle of a proof for M witnesses of ONE circuit
+// p2hot_commit_many and p2hot_prove_openings_many batch the two ends of M recursion-size proofs; these four batch what lies between:
+// partial products and Zs, the commitment of an interleaved device column set, the quotient with its gate constraints, the
+// OpeningSet.  Sigmas, constants, selectors, the gate set and k_is are shared; wires, challenges and the public-inputs hash are per
+// proof and reach the kernels through a device table indexed by blockIdx.y (plonk::ManyProof, gates::ManyGate).  Every argument is
+// checked before the first enqueue, a per-proof message names the proof, and each call synchronises once.
+
+// where proof j's block lies from proof 0's, in words: the kernels add it to proof 0's pointer, which they have as an argument
+static ptrdiff_t many_words_between(const u64 *p, const u64 *p0) { return (ptrdiff_t)(((intptr_t)p - (intptr_t)p0) / 8); }
+
+// the per-proof checks the M-forms share: entry j of `tab` is a commitment of this context with `ref`'s degree and rate
+static int many_check(p2hot_ctx *ctx, const char *what, const char *role, const p2hot_batch *const *tab, size_t M, const p2hot_batch *ref,
+                      size_t min_width) {
+    for (size_t j = 0; j < M; ++j) {
+        const p2hot_batch *b = tab[j];
+        if (!b) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: the %s commitment is null", what, j, role);
+        if (b->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: the %s commitment belongs to another context", what, j, role);
+        if (!ref) ref = tab[0];
+        if (b->log_n != ref->log_n || b->rate_bits != ref->rate_bits)
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: the %s commitment differs in degree or rate (2^%u rows, rate 2^%u; expected 2^%u, 2^%u)", what, j,
+                    role, b->log_n, b->rate_bits, ref->log_n, ref->rate_bits);
+        if (b->W < min_width) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: the %s commitment has %zu polynomials, %zu are needed", what, j, role, b->W, min_width);
+    }
+    return P2HOT_OK;
+}
+
+extern "C" int p2hot_partial_products_many(p2hot_ctx *ctx, size_t M, const p2hot_batch *const *wires, size_t wires_first_col,
+                                           const p2hot_cols *sigmas, size_t sigmas_first_col, const uint64_t *k_is, unsigned num_routed,
+                                           unsigned degree, const uint64_t *betas, const uint64_t *gammas, unsigned num_challenges,
+                                           uint64_t *out_host, p2hot_cols **out_cols) {
+    P2_ENTER(ctx);
+    const char *what = "partial_products_many";
+    if (out_cols) *out_cols = nullptr;
+    if (M == 0) return P2HOT_OK;
+    if (!wires || !sigmas || !k_is || !betas || !gammas) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null argument", what);
+    if (sigmas->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: the sigmas belong to another context", what);
+    if (num_challenges == 0 || num_challenges > 4) P2_FAIL(ctx, P2HOT_EINVAL, "%s: %u challenges (1..4)", what, num_challenges);
+    if (degree < 2 || !(degree < num_routed)) P2_FAIL(ctx, P2HOT_EINVAL, "%s: need 2 <= degree < num_routed", what);
+    P2_TRY(many_check(ctx, what, "wires", wires, M, nullptr, wires_first_col + num_routed));
+    const unsigned log_n = wires[0]->log_n, nc = num_challenges;
+    if (sigmas->log_n != log_n) P2_FAIL(ctx, P2HOT_EINVAL, "%s: wires and sigmas have different lengths", what);
+    if (sigmas_first_col > sigmas->W || num_routed > sigmas->W - sigmas_first_col)
+        P2_FAIL(ctx, P2HOT_EINVAL, "%s: %u routed columns do not fit the sigmas", what, num_routed);
+    if (M > 65535 || M * num_routed > 65535) P2_FAIL(ctx, P2HOT_EINVAL, "%s: M * num_routed = %zu polynomials exceed one launch (65535)", what, M * num_routed);
+    const size_t n = (size_t)1 << log_n;
+    const unsigned num_chunks = (num_routed + degree - 1) / degree, num_prods = num_chunks - 1;
+    const size_t rows = (size_t)nc * (num_prods + 1);
+    const unsigned chunk_log = log_n < 6 ? log_n : 6;  // rows per scan chunk (p2hot_partial_products_dev's)
+    const size_t n_chunks = n >> chunk_log, per = (n_chunks + 1023) / 1024;
+    // scratch: 2 x (chunk denominators [M][num_chunks][n] | row totals [M][n]) | chunk products [M][n_chunks] | carries | flags [M];
+    // small: k_is | the per-proof table
+    const size_t set_words = M * ((size_t)num_chunks * n + n), tab_words = M * sizeof(plonk::ManyProof) / 8;
+    PoolBuf d_out(ctx), d_vals(ctx), d_scr(ctx), d_small(ctx);
+    P2_TRY(pool_alloc(ctx, rows * M * n * 8, &d_out.p));
+    P2_TRY(pool_alloc(ctx, M * num_routed * n * 8, &d_vals.p));
+    P2_TRY(pool_alloc(ctx, (2 * set_words + 2 * M * n_chunks + M) * 8, &d_scr.p));
+    P2_TRY(pool_alloc(ctx, (num_routed + tab_words) * 8, &d_small.p));
+    std::vector<u64> small(num_routed + tab_words);
+    for (unsigned j = 0; j < num_routed; ++j) small[j] = gl::canon(k_is[j]);
+    plonk::ManyProof *tab = reinterpret_cast<plonk::ManyProof *>(small.data() + num_routed);
+    for (size_t j = 0; j < M; ++j) {
+        plonk::ManyProof t{};
+        t.coef_off = many_words_between(wires[j]->d_coef, wires[0]->d_coef), t.coef_stride = wires[j]->col_stride_coef();
+        for (unsigned c = 0; c < nc; ++c) t.betas[c] = gl::canon(betas[j * nc + c]), t.gammas[c] = gl::canon(gammas[j * nc + c]);
+        tab[j] = t;
+    }
+    u64 *d_k = d_small.u(), *sets = d_scr.u(), *prod = sets + 2 * set_words, *carry = prod + M * n_chunks;
+    unsigned *flags = (unsigned *)(carry + M * n_chunks);
+    const plonk::ManyProof *d_tab = reinterpret_cast<const plonk::ManyProof *>(d_small.u() + num_routed);
+    std::vector<unsigned> zero(M, 0);
+    auto body = [&]() -> int {
+        P2_HIP(ctx, hipMemcpyAsync(d_small.p, small.data(), small.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        P2_HIP(ctx, hipMemsetAsync(flags, 0, M * 8, ctx->stream));
+        // the routed wires' values on H: a forward NTT of a copy of every proof's coefficients (p2hot_batch_subgroup_values' route)
+        P2HOT_LAUNCH(plonk::many_gather_coeffs_kernel, dim3(cdiv(n, 256), num_routed, (unsigned)M), dim3(256), 0, ctx->stream, (const u64 *)wires[0]->d_coef, d_tab,
+                     wires_first_col, n, d_vals.u());
+        P2_LAUNCH_CHECK(ctx);
+        P2_TRY(p2hot_fft_dev(ctx, d_vals.u(), M * num_routed, n, log_n));
+        P2HOT_LAUNCH(ntt::canon_kernel, dim3(cdiv(M * num_routed * n, 256)), dim3(256), 0, ctx->stream, d_vals.u(), M * num_routed * n);
+        P2_LAUNCH_CHECK(ctx);
+        ProfScope ps(ctx, "partial_products_many");
+        std::vector<plonk::PPArgs> args(nc);
+        for (unsigned ch = 0; ch < nc; ++ch) {  // proof 0's blocks; the kernels step to proof blockIdx.y
+            plonk::PPArgs &a = args[ch];
+            u64 *dchunk = sets + (size_t)(ch & 1) * set_words;
+            a.wires = d_vals.u(), a.wires_stride = n;
+            a.sigmas = sigmas->d + sigmas_first_col * n, a.sigmas_stride = n;
+            a.k_is = d_k;
+            a.num_routed = num_routed, a.degree = degree, a.num_chunks = num_chunks, a.log_n = log_n;
+            a.beta = a.gamma = 0;
+            a.roots = ctx->fwd;
+            a.pp = d_out.u() + ((size_t)nc + (size_t)ch * num_prods) * M * n;  // interleaved: column e of proof m is column e * M + m
+            a.pp_stride = M * n;
+            a.dchunk = dchunk;
+            a.total = dchunk + M * (size_t)num_chunks * n;
+            a.zero_flag = flags;
+        }
+        const dim3 grid(cdiv(n, 256), (unsigned)M);
+        for (unsigned ch = 0; ch < nc; ++ch) {
+            const plonk::PPArgs &a = args[ch];
+            u64 *z = d_out.u() + (size_t)ch * M * n;
+            if (ctx->pp_streams && (ch & 1) == 0 && ch + 1 < nc) {  // a pair of challenges in one pass, as the single-proof call runs them
+                plonk::PPArgs2 two{{args[ch], args[ch + 1]}};
+                P2HOT_LAUNCH(plonk::pp_quotients2_many_kernel, grid, dim3(256), 0, ctx->stream, two, d_tab, ch, (size_t)num_routed * n);
+            } else if (!(ctx->pp_streams && (ch & 1))) {
+                P2HOT_LAUNCH(plonk::pp_quotients_many_kernel, grid, dim3(256), 0, ctx->stream, a, d_tab, ch, (size_t)num_routed * n);
+            }
+            // the proofs' rows lie back to back: chunk totals, the Z walk and the scaling run over M * n rows, the carries restart per proof
+            P2HOT_LAUNCH(plonk::pp_chunk_totals_kernel, dim3(cdiv(M * n_chunks, 256)), dim3(256), 0, ctx->stream, (const u64 *)a.total, chunk_log,
+                         M * n_chunks, prod);
+            P2HOT_LAUNCH(plonk::pp_carries_many_kernel, dim3(1, (unsigned)M), dim3(1024), 0, ctx->stream, (const u64 *)prod, n_chunks, per, carry);
+            P2HOT_LAUNCH(plonk::pp_emit_z_kernel, dim3(cdiv(M * n_chunks, 256)), dim3(256), 0, ctx->stream, (const u64 *)a.total, chunk_log,
+                         M * n_chunks, (const u64 *)carry, z);
+            if (num_prods)
+                P2HOT_LAUNCH(plonk::pp_scale_kernel, dim3(cdiv(M * n, 256)), dim3(256), 0, ctx->stream, a.pp, M * n, num_prods, (const u64 *)z, M * n);
+            P2_LAUNCH_CHECK(ctx);
+        }
+        if (out_host)  // [M][rows][n] <- [rows][M][n]: one strided copy per proof
+            for (size_t j = 0; j < M; ++j) P2_TRY(d2h_2d(ctx, out_host + j * rows * n, n * 8, d_out.u() + j * n, M * n * 8, n * 8, rows));
+        P2_TRY(d2h(ctx, zero.data(), flags, M * 4));
+        return P2HOT_OK;
+    };
+    int rc = sync_checked(ctx, body(), what);
+    if (rc != P2HOT_OK) return rc;
+    for (size_t j = 0; j < M; ++j)
+        if (zero[j]) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: tried to invert zero (a denominator wire + beta*sigma + gamma vanished)", what, j);
+    if (out_cols) {
+        *out_cols = new p2hot_cols{ctx, d_out.u(), rows * M, log_n, true};
+        d_out.p = nullptr;
+    }
+    return P2HOT_OK;
+}
+
+extern "C" int p2hot_commit_cols_many(p2hot_ctx *ctx, p2hot_cols *cols, size_t M, unsigned rate_bits, unsigned cap_height, int is_values,
+                                      uint64_t *caps_out, p2hot_batch **handles_out) {
+    P2_ENTER(ctx);
+    if (handles_out)
+        for (size_t m = 0; m < M; ++m) handles_out[m] = nullptr;
+    if (M == 0) return P2HOT_OK;  // nothing done, nothing consumed
+    // every argument is checked BEFORE the set is touched: P2HOT_EINVAL (and P2HOT_EBUSY) mean "not consumed" (p2hot_commit_cols' rule)
+    if (!cols) P2_FAIL(ctx, P2HOT_EINVAL, "commit_cols_many: null column set");
+    if (cols->ctx != ctx || !cols->owned) P2_FAIL(ctx, P2HOT_EINVAL, "commit_cols_many: the column set belongs to another context or is a borrowed view");
+    const unsigned log_n = cols->log_n, log_N = log_n + rate_bits;
+    P2_TRY(check_log(ctx, log_N, "commit_cols_many"));
+    if (M & (M - 1)) P2_FAIL(ctx, P2HOT_EINVAL, "commit_many: the number of proofs (%zu) must be a power of two", M);
+    if (cols->W == 0) P2_FAIL(ctx, P2HOT_EINVAL, "commit_many: no polynomials (the reference panics on polynomials[0], fri/oracle.rs:90)");
+    if (cols->W % M) P2_FAIL(ctx, P2HOT_EINVAL, "commit_cols_many: a set of %zu columns is not an interleaved set of %zu proofs", cols->W, M);
+    if (cols->W > 65535) P2_FAIL(ctx, P2HOT_EINVAL, "commit_many: W * M = %zu polynomials exceed one launch (65535)", cols->W);
+    if (cap_height > log_N) P2_FAIL(ctx, P2HOT_EINVAL, "commit_many: cap_height %u > log2(N) %u (merkle_tree.rs:195-200)", cap_height, log_N);
+    unsigned lm = 0;
+    while (((size_t)1 << lm) < M) ++lm;
+    P2_TRY(check_log(ctx, log_N + lm, "commit_cols_many"));
+    const size_t W = cols->W / M, n = (size_t)1 << log_n, N = n << rate_bits;
+    const size_t nd = p2hot_num_digests(log_N, cap_height), cap_words = (size_t)4 << cap_height;
+    PoolBuf d_co(ctx);
+    d_co.p = cols->d;
+    delete cols;  // consumed from here on: the block is ours whatever happens below
+    PoolBuf d_lde(ctx), d_dig(ctx), d_cap(ctx);
+    P2_TRY(pool_alloc(ctx, W * M * N * 8, &d_lde.p));
+    P2_TRY(pool_alloc(ctx, (nd ? nd : 1) * M * 32, &d_dig.p));
+    P2_TRY(pool_alloc(ctx, cap_words * M * 8, &d_cap.p));
+    auto body = [&]() -> int {
+        P2_TRY(p2hot_commit_many_dev(ctx, d_co.u(), M, W, log_n, rate_bits, cap_height, is_values, d_lde.u(), d_dig.u(), d_cap.u()));
+        if (caps_out) P2_TRY(d2h(ctx, caps_out, d_cap.p, cap_words * M * 8));
+        return P2HOT_OK;
+    };
+    int rc = sync_checked(ctx, body(), "commit_cols_many");
+    if (rc == P2HOT_OK && handles_out) {  // p2hot_commit_many's handles: shares of the blocks, freed with the last one
+        SharedBlocks *sh = new SharedBlocks;
+        sh->refs = (int)M;
+        sh->lde = d_lde.p, sh->dig = d_dig.p, sh->coef = d_co.p;
+        for (size_t m = 0; m < M; ++m) {
+            p2hot_batch *b = new p2hot_batch{ctx, d_lde.u() + m * N, W, N, d_dig.u() + m * nd * 4, log_N, cap_height};
+            b->d_coef = d_co.u() + m * n;
+            b->log_n = log_n;
+            b->rate_bits = rate_bits;
+            b->lde_stride = M * N;
+            b->coef_stride = M * n;
+            b->shared = sh;
+            handles_out[m] = b;
+        }
+        d_lde.p = d_dig.p = d_co.p = nullptr;  // owned by the handles now
+    }
+    return rc;
+}
+
+extern "C" int p2hot_quotient_polys_gates_many(p2hot_ctx *ctx, size_t M, const p2hot_batch *const *wires, const p2hot_batch *constants_sigmas,
+                                               size_t sigmas_first_col, const p2hot_batch *const *zs_partial_products, const uint64_t *k_is,
+                                               unsigned num_routed, unsigned quotient_degree_factor, const uint64_t *betas, const uint64_t *gammas,
+                                               const uint64_t *alphas, unsigned num_challenges, const p2hot_gate_set *gs,
+                                               const uint64_t *public_inputs_hashes, uint64_t *values_out, p2hot_cols **chunks_out) {
+    P2_ENTER(ctx);
+    const char *what = "quotient_polys_gates_many";
+    if (chunks_out) *chunks_out = nullptr;
+    if (M == 0) return P2HOT_OK;
+    if (!wires || !constants_sigmas || !zs_partial_products || !k_is || !betas || !gammas || !alphas) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null argument", what);
+    if (!chunks_out && !values_out) P2_FAIL(ctx, P2HOT_EINVAL, "%s: nothing asked for", what);
+    if (constants_sigmas->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: the constants_sigmas commitment belongs to another context", what);
+    const unsigned nc = num_challenges;
+    if (nc == 0 || nc > 4) P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: %u challenges (1..4 supported; plonky2's configs use 2)", what, nc);
+    if (quotient_degree_factor < 2 || num_routed == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: bad quotient degree factor or no routed wires", what);
+    unsigned qbits = 0;
+    while ((1u << qbits) < quotient_degree_factor) ++qbits;
+    const unsigned num_chunks = (num_routed + quotient_degree_factor - 1) / quotient_degree_factor, num_prods = num_chunks - 1;
+    P2_TRY(many_check(ctx, what, "wires", wires, M, constants_sigmas, num_routed));
+    P2_TRY(many_check(ctx, what, "zs_partial_products", zs_partial_products, M, constants_sigmas, (size_t)nc * (1 + num_prods)));
+    for (size_t j = 0; j < M; ++j)
+        if (gs && wires[j]->col_stride_lde() >> 32)
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: a wires column stride of %zu words (the gate kernels' M-form takes less than 2^32)", what, j,
+                    wires[j]->col_stride_lde());
+    for (size_t j = 1; j < M; ++j)
+        if (wires[j]->W != wires[0]->W) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: %zu wires, proof 0 has %zu (one circuit)", what, j, wires[j]->W, wires[0]->W);
+    if (qbits > constants_sigmas->rate_bits)
+        P2_FAIL(ctx, P2HOT_EINVAL, "%s: quotient degree 2^%u above the rate 2^%u (prover.rs:632-636)", what, qbits, constants_sigmas->rate_bits);
+    if (constants_sigmas->W < sigmas_first_col + num_routed) P2_FAIL(ctx, P2HOT_EINVAL, "%s: the constants_sigmas commitment is narrower than the permutation argument needs", what);
+    if (M > 65535 || M * nc * quotient_degree_factor > 65535)
+        P2_FAIL(ctx, P2HOT_EINVAL, "%s: W * M = %zu polynomials exceed one launch (65535)", what, M * nc * quotient_degree_factor);
+    unsigned gs_stride = 0;
+    if (gs) P2_TRY(gates_validate(ctx, gs, wires[0], constants_sigmas, sigmas_first_col, quotient_degree_factor, what, &gs_stride));
+    const unsigned degree_bits = constants_sigmas->log_n, log_nq = degree_bits + qbits;
+    P2_TRY(check_log(ctx, log_nq, what));
+    const size_t n = (size_t)1 << degree_bits, m = n << qbits, rate = (size_t)1 << qbits, keep = n * quotient_degree_factor;
+    // small: beta_c k_j [M][nc][num_routed] | Z_H and inverses [2 rate] | gate alpha powers [M][nc][gs_stride] | ManyProof [M] | ManyGate [M]
+    const size_t nbk = M * nc * num_routed, n_gpow = M * nc * gs_stride, w_tab = M * sizeof(plonk::ManyProof) / 8, w_gtab = M * sizeof(gates::ManyGate) / 8;
+    const size_t o_zh = nbk, o_gpow = o_zh + 2 * rate, o_tab = o_gpow + n_gpow, o_gtab = o_tab + w_tab;
+    std::vector<u64> small(o_gtab + w_gtab);
+    const u64 g_pow_n = gl::pow(gl::COSET_SHIFT, n), v = gl::root_of_unity(qbits);
+    for (size_t j = 0; j < rate; ++j) {
+        const u64 e = gl::canon(gl::sub(gl::mul(g_pow_n, gl::pow(v, j)), 1));
+        if (e == 0) P2_FAIL(ctx, P2HOT_EINVAL, "%s: Z_H vanishes on the coset", what);
+        small[o_zh + j] = e;
+        small[o_zh + rate + j] = gl::inv(e);
+    }
+    const u64 K = (u64)nc + (u64)nc * num_chunks;
+    plonk::ManyProof *tab = reinterpret_cast<plonk::ManyProof *>(small.data() + o_tab);
+    gates::ManyGate *gtab = reinterpret_cast<gates::ManyGate *>(small.data() + o_gtab);
+    for (size_t j = 0; j < M; ++j) {
+        const uint64_t *be = betas + j * nc, *ga = gammas + j * nc, *al = alphas + j * nc;
+        for (unsigned c = 0; c < nc; ++c)
+            for (unsigned r = 0; r < num_routed; ++r) small[(j * nc + c) * num_routed + r] = gl::canon(gl::mul(be[c], k_is[r]));
+        if (gs) gates_alpha_powers(small.data() + o_gpow + j * nc * gs_stride, al, nc, gs_stride);
+        plonk::ManyProof t{};
+        t.wires_off = many_words_between(wires[j]->d_lde, wires[0]->d_lde), t.wires_stride = wires[j]->col_stride_lde();
+        t.zs_off = many_words_between(zs_partial_products[j]->d_lde, zs_partial_products[0]->d_lde), t.zs_stride = zs_partial_products[j]->col_stride_lde();
+        for (unsigned a = 0; a < nc; ++a) {  // QuotArgs' per-challenge values, as quotient_polys_core fills them
+            t.betas[a] = be[a], t.gammas[a] = gl::canon(ga[a]), t.alphas[a] = al[a];
+            t.alpha_k[a] = gl::pow(al[a], K);
+            for (unsigned c = 0; c < nc; ++c) t.base[a][c] = gl::pow(al[a], (u64)nc + (u64)c * num_chunks);
+        }
+        gates::ManyGate g{};
+        g.wires_off = t.wires_off, g.wires_stride = (unsigned)t.wires_stride;
+        g.wires = wires[j]->d_lde, g.wires_stride64 = t.wires_stride;
+        for (unsigned k = 0; k < 4; ++k) {
+            const u64 h = public_inputs_hashes ? public_inputs_hashes[j * 4 + k] : gs ? gs->public_inputs_hash[k] : 0;
+            g.pih[k] = gl::canon(h);
+        }
+        tab[j] = t;
+        gtab[j] = g;
+    }
+    PoolBuf d_work(ctx), d_small(ctx), d_gate(ctx), d_chunks(ctx);
+    P2_TRY(pool_alloc(ctx, (M * nc * m + M) * 8, &d_work.p));  // the quotient values [M][nc][m], one flag word per proof behind them
+    P2_TRY(pool_alloc(ctx, small.size() * 8, &d_small.p));
+    if (gs) P2_TRY(pool_alloc(ctx, M * nc * m * 8, &d_gate.p));
+    if (chunks_out) P2_TRY(pool_alloc(ctx, M * nc * quotient_degree_factor * n * 8, &d_chunks.p));
+    // 1 / (n (x - 1)) for every point of the quotient coset: sizes only, kept by the context (quotient_polys_core's table)
+    const auto inv_key = std::make_tuple(100, log_nq, qbits);
+    auto inv_it = ctx->twid_cache.find(inv_key);
+    if (inv_it == ctx->twid_cache.end()) {
+        u64 *t = nullptr;
+        P2_HIP(ctx, hipMalloc((void **)&t, m * 8));
+        P2HOT_LAUNCH(plonk::quot_inv_kernel, dim3(cdiv(m, 256)), dim3(256), 0, ctx->stream, t, log_nq, (u64)n % gl::P, ctx->fwd);
+        if (hipGetLastError() != hipSuccess) {
+            (void)hipFree(t);
+            P2_FAIL(ctx, P2HOT_EHIP, "%s: the L_0 denominator table could not be launched", what);
+        }
+        inv_it = ctx->twid_cache.emplace(inv_key, t).first;
+    }
+    plonk::QuotArgs q{};  // the shared fields and proof 0's matrices; the kernel takes the rest from the table
+    q.wires = wires[0]->d_lde, q.zs = zs_partial_products[0]->d_lde;
+    q.sigmas = constants_sigmas->d_lde + sigmas_first_col * constants_sigmas->col_stride_lde(), q.sigmas_stride = constants_sigmas->col_stride_lde();
+    q.bk = d_small.u(), q.zh = d_small.u() + o_zh, q.inv_nx1 = inv_it->second;
+    q.gate_sums = gs ? d_gate.u() : nullptr;
+    q.out = d_work.u();
+    q.num_routed = num_routed, q.degree = quotient_degree_factor, q.num_chunks = num_chunks, q.log_nq = log_nq, q.qbits = qbits;
+    q.roots = ctx->fwd;
+    const plonk::ManyProof *d_tab = reinterpret_cast<const plonk::ManyProof *>(d_small.u() + o_tab);
+    const gates::ManyGate *d_gtab = reinterpret_cast<const gates::ManyGate *>(d_small.u() + o_gtab);
+    unsigned *flags = (unsigned *)(d_work.u() + M * nc * m);
+    std::vector<unsigned> nonzero(M, 0);
+    auto body = [&]() -> int {
+        P2_HIP(ctx, hipMemcpyAsync(d_small.p, small.data(), small.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (gs) {
+            P2_HIP(ctx, hipMemsetAsync(d_gate.p, 0, M * nc * m * 8, ctx->stream));
+            P2_TRY(gates_launch(ctx, gs, wires[0], constants_sigmas, d_small.u() + o_gpow, gs_stride, d_gate.u(), log_nq, nc, d_gtab, M));
+        }
+        {
+            ProfScope prof(ctx, "quotient_perm_many");
+            const dim3 grid(cdiv(m, 256), (unsigned)M), block(256);
+            if (nc == 2 && quotient_degree_factor == 8) {  // the pipelined instantiation, as the single-proof call chooses it
+                P2HOT_LAUNCH((plonk::quotient_perm_many_kernel<2, 8>), grid, block, 0, ctx->stream, q, d_tab);
+            } else {
+                switch (nc) {
+                    case 1: P2HOT_LAUNCH((plonk::quotient_perm_many_kernel<1, 0>), grid, block, 0, ctx->stream, q, d_tab); break;
+                    case 2: P2HOT_LAUNCH((plonk::quotient_perm_many_kernel<2, 0>), grid, block, 0, ctx->stream, q, d_tab); break;
+                    case 3: P2HOT_LAUNCH((plonk::quotient_perm_many_kernel<3, 0>), grid, block, 0, ctx->stream, q, d_tab); break;
+                    default: P2HOT_LAUNCH((plonk::quotient_perm_many_kernel<4, 0>), grid, block, 0, ctx->stream, q, d_tab); break;
+                }
+            }
+            P2_LAUNCH_CHECK(ctx);
+        }
+        if (values_out) P2_HIP(ctx, hipMemcpyAsync(values_out, d_work.p, M * nc * m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (!chunks_out) return P2HOT_OK;
+        // values.coset_ifft(F::coset_shift()) on all M * nc polynomials, trim_to_len with one divisibility flag per proof, and the
+        // chunks straight into the interleaved layout (quotient_chunks_core's steps)
+        P2_TRY(p2hot_coset_ifft_dev(ctx, d_work.u(), M * nc, m, log_nq, gl::COSET_SHIFT));
+        P2_HIP(ctx, hipMemsetAsync(flags, 0, M * 8, ctx->stream));
+        if (keep < m) {
+            P2HOT_LAUNCH(plonk::any_nonzero_many_kernel, dim3(cdiv(m - keep, 256), nc, (unsigned)M), dim3(256), 0, ctx->stream, (const u64 *)d_work.u(), m,
+                         keep, flags);
+            P2_LAUNCH_CHECK(ctx);
+        }
+        P2HOT_LAUNCH(plonk::chunks_interleave_kernel, dim3(cdiv(n, 256), nc * quotient_degree_factor, (unsigned)M), dim3(256), 0, ctx->stream,
+                     (const u64 *)d_work.u(), m, n, quotient_degree_factor, nc, d_chunks.u());
+        P2_LAUNCH_CHECK(ctx);
+        P2_TRY(d2h(ctx, nonzero.data(), flags, M * 4));
+        return P2HOT_OK;
+    };
+    int rc = sync_checked(ctx, body(), what);
+    if (rc != P2HOT_OK) return rc;
+    for (size_t j = 0; j < M; ++j)
+        if (nonzero[j]) P2_FAIL(ctx, P2HOT_EINVAL, "Quotient has failed, the vanishing polynomial is not divisible by Z_H (proof %zu)", j);
+    if (chunks_out) {
+        *chunks_out = new p2hot_cols{ctx, d_chunks.u(), (size_t)nc * quotient_degree_factor * M, degree_bits, true};
+        d_chunks.p = nullptr;
+    }
+    return P2HOT_OK;
+}
+
+extern "C" int p2hot_eval_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_batch *const *batches, size_t n_batches, const uint64_t *points,
+                                        size_t n_points, uint64_t *out) {
+    P2_ENTER(ctx);
+    const char *what = "eval_openings_many";
+    if (M == 0 || n_batches == 0 || n_points == 0) return P2HOT_OK;
+    if (!batches || !points || !out) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null argument", what);
+    if (M > 0x7FFFFFFFull / n_batches) P2_FAIL(ctx, P2HOT_EINVAL, "%s: too many oracles", what);
+    for (size_t j = 0; j < M; ++j)
+        for (size_t b = 0; b < n_batches; ++b) {
+            const p2hot_batch *B = batches[j * n_batches + b];
+            if (!B || B->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: oracle %zu is null or belongs to another context", what, j, b);
+            if (B->log_n != batches[0]->log_n)
+                P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: all oracles must have the same degree (oracle %zu: 2^%u vs 2^%u)", what, j, b, B->log_n,
+                        batches[0]->log_n);
+        }
+    const unsigned log_n = batches[0]->log_n;
+    P2_TRY(check_log(ctx, log_n, what));
+    // every polynomial of every proof in order, with the proof it belongs to: one launch per stage for all proofs and points
+    std::vector<const u64 *> ptrs;
+    std::vector<unsigned> grp;
+    for (size_t j = 0; j < M; ++j)
+        for (size_t b = 0; b < n_batches; ++b) {
+            const p2hot_batch *B = batches[j * n_batches + b];
+            for (size_t c = 0; c < B->W; ++c) ptrs.push_back(B->d_coef + c * B->col_stride_coef()), grp.push_back((unsigned)j);
+        }
+    const size_t total = ptrs.size();
+    if (total == 0) return P2HOT_OK;
+    const size_t n = (size_t)1 << log_n;
+    const unsigned seg_log = log_n < 12 ? log_n : 12;  // p2hot_eval_polys_dev's segments
+    const size_t n_seg = n >> seg_log, seg = (size_t)1 << seg_log, G = M * n_points;
+    if (total > 0x7FFFFFFFull || n_seg > 65535 || n_points > 65535 || G > 65535) P2_FAIL(ctx, P2HOT_EINVAL, "%s: too many polynomials, points or proofs for one launch", what);
+    // host blob: pointers [total] | proof of polynomial [total] (u32) | points [G][2] | (z^seg, (z^seg)^256) [G][4]
+    const size_t o_grp = total, o_pts = o_grp + (total + 1) / 2, o_zs = o_pts + 2 * G, blob_words = o_zs + 4 * G;
+    std::vector<u64> blob(blob_words);
+    std::copy(ptrs.begin(), ptrs.end(), reinterpret_cast<const u64 **>(blob.data()));
+    std::copy(grp.begin(), grp.end(), reinterpret_cast<unsigned *>(blob.data() + o_grp));
+    for (size_t g = 0; g < G; ++g) {
+        const gl::ext2 z{gl::canon(points[2 * g]), gl::canon(points[2 * g + 1])};
+        const gl::ext2 zs = ext_pow(z, (u64)1 << seg_log), zs256 = ext_pow(zs, 256);
+        blob[o_pts + 2 * g] = z.a0, blob[o_pts + 2 * g + 1] = z.a1;
+        blob[o_zs + 4 * g] = gl::canon(zs.a0), blob[o_zs + 4 * g + 1] = gl::canon(zs.a1);
+        blob[o_zs + 4 * g + 2] = gl::canon(zs256.a0), blob[o_zs + 4 * g + 3] = gl::canon(zs256.a1);
+    }
+    PoolBuf d_blob(ctx), d_w(ctx), d_part(ctx), d_res(ctx);
+    P2_TRY(pool_alloc(ctx, blob_words * 8, &d_blob.p));
+    P2_TRY(pool_alloc(ctx, G * 2 * seg * 8, &d_w.p));
+    P2_TRY(pool_alloc(ctx, n_points * total * n_seg * 16, &d_part.p));
+    P2_TRY(pool_alloc(ctx, n_points * total * 16, &d_res.p));
+    std::vector<u64> res(n_points * total * 2);  // device layout [n_points][total][2]
+    auto body = [&]() -> int {
+        P2_HIP(ctx, hipMemcpyAsync(d_blob.p, blob.data(), blob_words * 8, hipMemcpyHostToDevice, ctx->stream));
+        const u64 *const *d_ptrs = reinterpret_cast<const u64 *const *>(d_blob.u());
+        const unsigned *d_grp = reinterpret_cast<const unsigned *>(d_blob.u() + o_grp);
+        ProfScope ps(ctx, "eval_polys_many");
+        P2HOT_LAUNCH(fri::ext_powers_many_kernel, dim3(cdiv(seg, 256), (unsigned)G), dim3(256), 0, ctx->stream, (const u64 *)(d_blob.u() + o_pts),
+                     (unsigned)seg, d_w.u());
+        P2HOT_LAUNCH(fri::eval_polys_dot_many_kernel, dim3((unsigned)total, (unsigned)n_seg, (unsigned)n_points), dim3(256), 0, ctx->stream, d_ptrs,
+                     d_grp, seg_log, (const u64 *)d_w.u(), d_part.u());
+        P2HOT_LAUNCH(fri::eval_polys_stage2_many_kernel, dim3((unsigned)total, (unsigned)n_points), dim3(256), 0, ctx->stream, (const u64 *)d_part.u(),
+                     d_grp, n_seg, (const u64 *)(d_blob.u() + o_zs), d_res.u());
+        P2_LAUNCH_CHECK(ctx);
+        P2_HIP(ctx, hipMemcpyAsync(res.data(), d_res.p, res.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return P2HOT_OK;
+    };
+    int rc = sync_checked(ctx, body(), what);
+    if (rc != P2HOT_OK) return rc;
+    // the caller's layout: per proof, per oracle [n_points][W_o][2] (p2hot_eval_openings'), the proofs back to back
+    size_t off = 0, out_off = 0;
+    for (size_t j = 0; j < M; ++j)
+        for (size_t b = 0; b < n_batches; ++b) {
+            const size_t W = batches[j * n_batches + b]->W;
+            for (size_t p = 0; p < n_points; ++p) std::copy(res.begin() + 2 * (p * total + off), res.begin() + 2 * (p * total + off + W), out + out_off + 2 * p * W);
+            off += W;
+            out_off += 2 * n_points * W;
+        }
     return P2HOT_OK;
 }

@@ -37,36 +37,7 @@ struct PPArgs {
 
 // lane = row: prefix quotients Q_c(i) = prod_{k <= c} chunk_k(i) for c < num_chunks - 1, and T_i = Q_last(i)
 __global__ void __launch_bounds__(256) pp_quotients_kernel(PPArgs a) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t n = (size_t)1 << a.log_n;
-    if (i >= n) return;
-    const u64 x = a.log_n ? ntt::root_pow(a.roots, (u32)(i << (32 - a.log_n))) : 1;
-    const u64 bx = gl::mul(a.beta, x);
-    u64 pn = 1, pd = 1;
-    for (unsigned c = 0; c < a.num_chunks; ++c) {
-        u64 d = 1;
-        const unsigned j_end = (c + 1) * a.degree < a.num_routed ? (c + 1) * a.degree : a.num_routed;
-        for (unsigned j = c * a.degree; j < j_end; ++j) {
-            const u64 w = a.wires[(size_t)j * a.wires_stride + i];
-            const u64 num = gl::add(gl::add(w, gl::mul(bx, a.k_is[j])), a.gamma);
-            const u64 den = gl::add(gl::add(w, gl::mul(a.beta, a.sigmas[(size_t)j * a.sigmas_stride + i])), a.gamma);
-            pn = gl::mul(pn, num);
-            d = gl::mul(d, den);
-        }
-        pd = gl::mul(pd, d);
-        a.dchunk[(size_t)c * n + i] = d;
-        if (c + 1 < a.num_chunks) a.pp[(size_t)c * a.pp_stride + i] = pn;
-    }
-    if (gl::canon(pd) == 0) atomicOr(a.zero_flag, 1u);
-    u64 inv = gl::inv(pd);  // PD_last^-1
-    a.total[i] = gl::mul(pn, inv);
-    for (unsigned c = a.num_chunks; c-- > 0;) {
-        if (c + 1 < a.num_chunks) {
-            u64 *q = a.pp + (size_t)c * a.pp_stride + i;
-            *q = gl::mul(*q, inv);
-        }
-        inv = gl::mul(inv, a.dchunk[(size_t)c * n + i]);
-    }
+#include "kbody_pp_quotients.hpp"
 }
 
 // Both challenges of a plonky2 config in ONE pass over the wires and sigmas, all multiplications as gl_mul3.hpp streams (the
@@ -77,81 +48,52 @@ struct PPArgs2 {
 };
 __global__ void __launch_bounds__(256) pp_quotients2_kernel(PPArgs2 aa) {
     const PPArgs &a = aa.c[0], &b = aa.c[1];
+#include "kbody_pp_quotients2.hpp"
+}
+
+// ------------------------------------------------------------------ M witnesses of one circuit (p2hot_partial_products_many, p2hot_quotient_polys_gates_many)
+// What differs between the proofs of one call, one entry per proof in device memory.  A kernel's M-form takes the shared arguments
+// by value as its single-proof form does, runs one grid row (blockIdx.y) per proof and takes the per-proof fields from
+// tab[blockIdx.y]: the index is wave-uniform and the table read-only, so these are scalar loads into SGPRs, where the single-proof
+// form finds its kernel arguments.  Z_H and the 1 / (n (x - 1)) table depend on the sizes only and stay shared.
+// The kernels' bodies are the kbody_*.hpp fragments, #included by both forms: the single-proof kernels keep their tokens and with
+// them their code.
+// (A pointer read from the table would have no known address space and cost flat loads: the table holds each block's OFFSET in
+// words from proof 0's block, which the kernel has as an argument.)
+struct ManyProof {
+    ptrdiff_t wires_off, zs_off, coef_off;  // this proof's wires / Zs LDE matrices and wires coefficients, from proof 0's
+    size_t wires_stride, zs_stride, coef_stride;
+    u64 betas[4], gammas[4], alphas[4];          // as the single-proof arguments carry them (gammas canonical)
+    u64 base[4][4], alpha_k[4];                  // QuotArgs' tables for this proof's alphas
+};
+
+// the routed wires' coefficients of every proof into one block [M][num_routed][n] (grid: rows, routed wire, proof), for one forward NTT
+__global__ void __launch_bounds__(256) many_gather_coeffs_kernel(const u64 *coef0, const ManyProof *__restrict__ tab, size_t first_col, size_t n,
+                                                                 u64 *out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t n = (size_t)1 << a.log_n;
     if (i >= n) return;
-    const u64 x = a.log_n ? ntt::root_pow(a.roots, (u32)(i << (32 - a.log_n))) : 1;
-    const u64 beta[2] = {a.beta, b.beta}, gamma[2] = {a.gamma, b.gamma};  // canonical (the host canonicalises)
-    u64 bx[2];
-    {
-        const u64 xx[2] = {x, x};
-        gl::mul2(beta, xx, bx);
-    }
-    u64 pn[2] = {1, 1}, pd[2] = {1, 1};
-    for (unsigned c = 0; c < a.num_chunks; ++c) {
-        u64 d[2] = {1, 1};
-        const unsigned j_end = (c + 1) * a.degree < a.num_routed ? (c + 1) * a.degree : a.num_routed;
-        for (unsigned j = c * a.degree; j < j_end; ++j) {
-            const u64 w = a.wires[(size_t)j * a.wires_stride + i], sg = a.sigmas[(size_t)j * a.sigmas_stride + i], kj = a.k_is[j];
-            const u64 wg0 = gl::add_canon(w, gamma[0]), wg1 = gl::add_canon(w, gamma[1]);
-            const u64 a1[3] = {bx[0], bx[1], beta[0]}, b1[3] = {kj, kj, sg}, c1[3] = {wg0, wg1, wg0};
-            u64 r1[3];
-            gl::mad3(a1, b1, c1, r1);  // num0, num1, den0
-            const u64 a2[3] = {beta[1], pn[0], pn[1]}, b2[3] = {sg, r1[0], r1[1]}, c2[3] = {wg1, 0, 0};
-            u64 r2[3];
-            gl::mad3(a2, b2, c2, r2);  // den1, pn0 num0, pn1 num1
-            pn[0] = r2[1], pn[1] = r2[2];
-            const u64 b3[2] = {r1[2], r2[0]};
-            u64 r3[2];
-            gl::mul2(d, b3, r3);
-            d[0] = r3[0], d[1] = r3[1];
-        }
-        gl::mul2(pd, d, pd);
-        a.dchunk[(size_t)c * n + i] = d[0];
-        b.dchunk[(size_t)c * n + i] = d[1];
-        if (c + 1 < a.num_chunks) {
-            a.pp[(size_t)c * a.pp_stride + i] = pn[0];
-            b.pp[(size_t)c * b.pp_stride + i] = pn[1];
-        }
-    }
-    if (gl::canon(pd[0]) == 0 || gl::canon(pd[1]) == 0) atomicOr(a.zero_flag, 1u);
-    // pd^(P-2) for both challenges at once.  P - 2 = (2^31 - 1) * 2^33 + (2^32 - 1): an addition chain of 64 squarings and 9
-    // multiplications (x^(2^k - 1) for k = 2, 3, 6, 12, 24, 30, 31, 32) instead of square-and-multiply's 63 + 62
-    u64 inv[2];
-    {
-        auto sqn = [](u64 v[2], int k) {
-            for (int t = 0; t < k; ++t) gl::mul2(v, v, v);
-        };
-        u64 t2[2] = {pd[0], pd[1]}, t3[2], t6[2], t12[2], t24[2], t[2];
-        sqn(t2, 1), gl::mul2(t2, pd, t2);                                   // 2^2 - 1
-        t3[0] = t2[0], t3[1] = t2[1], sqn(t3, 1), gl::mul2(t3, pd, t3);     // 2^3 - 1
-        t6[0] = t3[0], t6[1] = t3[1], sqn(t6, 3), gl::mul2(t6, t3, t6);     // 2^6 - 1
-        t12[0] = t6[0], t12[1] = t6[1], sqn(t12, 6), gl::mul2(t12, t6, t12);
-        t24[0] = t12[0], t24[1] = t12[1], sqn(t24, 12), gl::mul2(t24, t12, t24);
-        t[0] = t24[0], t[1] = t24[1], sqn(t, 6), gl::mul2(t, t6, t);        // 2^30 - 1
-        sqn(t, 1), gl::mul2(t, pd, t);                                      // a = x^(2^31 - 1)
-        u64 b[2] = {t[0], t[1]};
-        sqn(b, 1), gl::mul2(b, pd, b);                                      // b = x^(2^32 - 1)
-        sqn(t, 33);
-        gl::mul2(t, b, inv);
-    }
-    {
-        u64 t[2];
-        gl::mul2(pn, inv, t);
-        a.total[i] = t[0];
-        b.total[i] = t[1];
-    }
-    for (unsigned c = a.num_chunks; c-- > 0;) {
-        if (c + 1 < a.num_chunks) {
-            u64 *q0 = a.pp + (size_t)c * a.pp_stride + i, *q1 = b.pp + (size_t)c * b.pp_stride + i;
-            const u64 qq[2] = {*q0, *q1};
-            u64 t[2];
-            gl::mul2(qq, inv, t);
-            *q0 = t[0], *q1 = t[1];
-        }
-        const u64 dd[2] = {a.dchunk[(size_t)c * n + i], b.dchunk[(size_t)c * n + i]};
-        gl::mul2(inv, dd, inv);
-    }
+    const ManyProof &t = tab[blockIdx.z];
+    out[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * n + i] = (coef0 + t.coef_off)[(first_col + blockIdx.y) * t.coef_stride + i];
+}
+
+// pp_quotients_kernel / pp_quotients2_kernel for proof blockIdx.y: the shared PPArgs describe proof 0's blocks, proof y's lie
+// `wires_step` (the gathered values), n (a column of the interleaved output; the row totals) and num_chunks * n (the chunk
+// denominators) further per proof; challenge `ch` of the proof's own (beta, gamma); one zero-denominator flag word per proof
+__device__ __forceinline__ void many_patch(PPArgs &a, const ManyProof &t, unsigned ch, size_t wires_step) {
+    const size_t y = blockIdx.y, n = (size_t)1 << a.log_n;
+    a.wires += y * wires_step;
+    a.beta = t.betas[ch], a.gamma = t.gammas[ch];
+    a.pp += y * n, a.dchunk += y * a.num_chunks * n, a.total += y * n, a.zero_flag += y;
+}
+__global__ void __launch_bounds__(256) pp_quotients_many_kernel(PPArgs a, const ManyProof *__restrict__ tab, unsigned ch, size_t wires_step) {
+    many_patch(a, tab[blockIdx.y], ch, wires_step);
+#include "kbody_pp_quotients.hpp"
+}
+__global__ void __launch_bounds__(256) pp_quotients2_many_kernel(PPArgs2 aa, const ManyProof *__restrict__ tab, unsigned ch, size_t wires_step) {
+    PPArgs &a = aa.c[0], &b = aa.c[1];
+    many_patch(a, tab[blockIdx.y], ch, wires_step);
+    many_patch(b, tab[blockIdx.y], ch + 1, wires_step);
+#include "kbody_pp_quotients2.hpp"
 }
 
 // lane = chunk of 2^chunk_log rows: its product
@@ -166,25 +108,13 @@ __global__ void pp_chunk_totals_kernel(const u64 *total, unsigned chunk_log, siz
 
 // carry[m] = prod_{m' < m} P[m'] (exclusive prefix product); one 1024-thread block, `per` consecutive chunks per thread
 __global__ void __launch_bounds__(1024) pp_carries_kernel(const u64 *prod, size_t n_chunks, size_t per, u64 *carry) {
-    __shared__ u64 s[1024];
-    const unsigned tid = threadIdx.x;
-    const size_t lo = (size_t)tid * per, hi = lo + per < n_chunks ? lo + per : n_chunks;
-    u64 loc = 1;
-    for (size_t m = lo; m < hi; ++m) loc = gl::mul(loc, prod[m]);
-    s[tid] = loc;
-    __syncthreads();
-    for (unsigned d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
-        u64 f = 1;
-        if (tid >= d) f = s[tid - d];
-        __syncthreads();
-        s[tid] = gl::mul(s[tid], f);
-        __syncthreads();
-    }
-    u64 c = tid ? s[tid - 1] : 1;
-    for (size_t m = lo; m < hi; ++m) {
-        carry[m] = c;
-        c = gl::mul(c, prod[m]);
-    }
+#include "kbody_pp_carries.hpp"
+}
+// one scan per proof: workgroup y scans proof y's n_chunks chunk products.  (The chunk totals, the Z walk and the scaling need no
+// M-form: with the proofs' rows back to back they are the single-proof kernels over M * n rows -- only the carries restart.)
+__global__ void __launch_bounds__(1024) pp_carries_many_kernel(const u64 *prod, size_t n_chunks, size_t per, u64 *carry) {
+    prod += (size_t)blockIdx.y * n_chunks, carry += (size_t)blockIdx.y * n_chunks;
+#include "kbody_pp_carries.hpp"
 }
 
 // lane = chunk: Z(x_i) for its rows from the chunk's carry (Z(x_0) = 1)
@@ -214,6 +144,21 @@ __global__ void pp_scale_kernel(u64 *pp, size_t pp_stride, unsigned num_prods, c
 __global__ void any_nonzero_kernel(const u64 *v, size_t count, unsigned *flag) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count && gl::canon(v[i]) != 0) atomicOr(flag, 1u);
+}
+
+// the divisibility check for M proofs: polynomial (proof z, challenge y) is column z * nc + y of `v` (m coefficients each); a nonzero
+// coefficient at or behind `keep` raises flags[z].  grid: (tail, challenge, proof)
+__global__ void any_nonzero_many_kernel(const u64 *v, size_t m, size_t keep, unsigned *flags) {
+    const size_t i = keep + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m && gl::canon(v[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * m + i]) != 0) atomicOr(flags + blockIdx.z, 1u);
+}
+// trim_to_len + chunks(n) for M proofs into the interleaved layout of p2hot_commit_many_dev: chunk k of polynomial (proof z,
+// challenge c) is column e = c * qdf + k of proof z, which is column e * M + z of the set.  grid: (rows, nc * qdf, M); canonical
+__global__ void __launch_bounds__(256) chunks_interleave_kernel(const u64 *v, size_t m, size_t n, unsigned qdf, unsigned nc, u64 *out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned e = blockIdx.y, c = e / qdf, k = e % qdf;
+    out[((size_t)e * gridDim.z + blockIdx.z) * n + i] = gl::canon(v[((size_t)blockIdx.z * nc + c) * m + (size_t)k * n + i]);
 }
 
 // ------------------------------------------------------------------ the permutation argument's share of the quotient
@@ -259,155 +204,32 @@ __global__ void __launch_bounds__(256) quot_inv_kernel(u64 *out, unsigned log_nq
 // for each pair of loads.  DEG == 0: any degree, plain loop.
 template <int NC, int DEG>
 __global__ void __launch_bounds__(256) quotient_perm_kernel(QuotArgs q) {
-    const size_t L = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = (size_t)1 << q.log_nq;
-    if (L >= nq) return;
-    const size_t i = q.log_nq ? (size_t)(__brevll((unsigned long long)L) >> (64 - q.log_nq)) : 0;
-    const size_t i_next = (i + ((size_t)1 << q.qbits)) & (nq - 1);
-    const size_t L_next = q.log_nq ? (size_t)(__brevll((unsigned long long)i_next) >> (64 - q.log_nq)) : 0;
-    const u64 x = gl::mul(gl::COSET_SHIFT, q.log_nq ? ntt::root_pow(q.roots, (u32)(i << (32 - q.log_nq))) : (u64)1);
-    const size_t r = i & (((size_t)1 << q.qbits) - 1);
-    // L_0(x) = Z_H(x) / (n (x - 1))  (zero_poly_coset.rs:58-61)
-    const u64 l0 = gl::mul(q.zh[r], q.inv_nx1[L]);
-    const unsigned num_prods = q.num_chunks - 1;
-    const unsigned degree = DEG ? (unsigned)DEG : q.degree;
-    u64 zx[NC], acc[NC][NC], pw[NC], res[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        zx[c] = q.zs[(size_t)c * q.zs_stride + L];
-#pragma unroll
-        for (int a = 0; a < NC; ++a) acc[a][c] = 0;
-        pw[c] = 1;  // alpha_c^chunk
-    }
-    // terms 0 .. NC-1: L_0(x) (Z_c(x) - 1)
-#pragma unroll
-    for (int a = 0; a < NC; ++a) {
-        u64 s = 0, p = 1;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            s = gl::mul_add(gl::mul(l0, gl::sub(zx[c], 1)), p, s);
-            p = gl::mul(p, q.alphas[a]);
-        }
-        res[a] = s;
-    }
-    u64 prev[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) prev[c] = zx[c];
-    constexpr int BUF = DEG ? DEG : 1;
-    u64 wb[BUF], sb[BUF];  // the chunk in flight (DEG > 0)
-    if (DEG) {
-#pragma unroll
-        for (int t = 0; t < BUF; ++t) {
-            const unsigned j = (unsigned)t < q.num_routed ? (unsigned)t : q.num_routed - 1;
-            wb[t] = q.wires[(size_t)j * q.wires_stride + L];
-            sb[t] = q.sigmas[(size_t)j * q.sigmas_stride + L];
-        }
-    }
-    for (unsigned ch = 0; ch < q.num_chunks; ++ch) {
-        u64 pn[NC], pd[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) pn[c] = pd[c] = 1;
-        const unsigned j0 = ch * degree, j_end = j0 + degree < q.num_routed ? j0 + degree : q.num_routed;
-        // the "next" value of this chunk's check (a partial product of x, or Z(g x) for the last chunk): loaded early too
-        u64 nextv[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-            nextv[c] = ch == num_prods ? q.zs[(size_t)c * q.zs_stride + L_next] : q.zs[((size_t)NC + (size_t)c * num_prods + ch) * q.zs_stride + L];
-        if (DEG) {
-            u64 wc[BUF], sc[BUF];
-#pragma unroll
-            for (int t = 0; t < BUF; ++t) wc[t] = wb[t], sc[t] = sb[t];
-            if (ch + 1 < q.num_chunks) {  // the next chunk's loads go out before this chunk's arithmetic
-#pragma unroll
-                for (int t = 0; t < BUF; ++t) {
-                    const unsigned jn = j0 + degree + (unsigned)t, j = jn < q.num_routed ? jn : q.num_routed - 1;
-                    wb[t] = q.wires[(size_t)j * q.wires_stride + L];
-                    sb[t] = q.sigmas[(size_t)j * q.sigmas_stride + L];
-                }
-            }
-            if constexpr (NC == 2) {
-                // eight multiplications per routed wire as hand-scheduled streams (gl_mul3.hpp: 14 instructions each, where the
-                // compiler's 64-bit code spends ~34 per multiply-reduce here): {bk0 x + wg0, bk1 x + wg1, beta0 sigma + wg0}, then
-                // {beta1 sigma + wg1, pn0 n0, pn1 n1}, then {pd0 d0, pd1 d1}
-#pragma unroll
-                for (int t = 0; t < BUF; ++t) {
-                    if (j0 + (unsigned)t < j_end) {
-                        const u64 wg0 = gl::add_canon(wc[t], q.gammas[0]), wg1 = gl::add_canon(wc[t], q.gammas[1]);
-                        // (the additions ride the streams' multiply-adds: gl::mad3)
-                        const u64 a1[3] = {q.bk[j0 + t], q.bk[(size_t)q.num_routed + j0 + t], q.betas[0]}, b1[3] = {x, x, sc[t]}, c1[3] = {wg0, wg1, wg0};
-                        u64 r1[3];
-                        gl::mad3(a1, b1, c1, r1);  // n0, n1, d0
-                        const u64 a2[3] = {q.betas[1], pn[0], pn[1]}, b2[3] = {sc[t], r1[0], r1[1]}, c2[3] = {wg1, 0, 0};
-                        u64 r2[3];
-                        gl::mad3(a2, b2, c2, r2);  // d1, pn0 n0, pn1 n1
-                        pn[0] = r2[1], pn[1] = r2[2];
-                        const u64 d0 = r1[2], d1 = r2[0];
-                        const u64 a3[2] = {pd[0], pd[1]}, b3[2] = {d0, d1};
-                        u64 r3[2];
-                        gl::mul2(a3, b3, r3);
-                        pd[0] = r3[0], pd[1] = r3[1];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < BUF; ++t) {
-                    if (j0 + (unsigned)t < j_end) {
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) {
-                            const u64 wg = gl::add(wc[t], q.gammas[c]);
-                            pn[c] = gl::mul(pn[c], gl::mul_add(q.bk[(size_t)c * q.num_routed + j0 + t], x, wg));
-                            pd[c] = gl::mul(pd[c], gl::mul_add(q.betas[c], sc[t], wg));
-                        }
-                    }
-                }
-            }
-        } else {
-            for (unsigned j = j0; j < j_end; ++j) {
-                const u64 w = q.wires[(size_t)j * q.wires_stride + L], sg = q.sigmas[(size_t)j * q.sigmas_stride + L];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) {
-                    const u64 wg = gl::add(w, q.gammas[c]);
-                    pn[c] = gl::mul(pn[c], gl::mul_add(q.bk[(size_t)c * q.num_routed + j], x, wg));
-                    pd[c] = gl::mul(pd[c], gl::mul_add(q.betas[c], sg, wg));
-                }
-            }
-        }
-        if constexpr (NC == 2 && DEG != 0) {  // the chunk's check and its place in the alpha sums, as streams too
-            const u64 a1[3] = {prev[0], prev[1], nextv[0]}, b1[3] = {pn[0], pn[1], pd[0]};
-            u64 r1[3];
-            gl::mul3(a1, b1, r1);
-            const u64 a2[3] = {nextv[1], pw[0], pw[1]}, b2[3] = {pd[1], q.alphas[0], q.alphas[1]}, z3[3] = {0, 0, 0};
-            u64 r2[3];
-            gl::mad3(a2, b2, z3, r2);
-            const u64 term0 = gl::sub(r1[0], r1[2]), term1 = gl::sub(r1[1], r2[0]);
-            const u64 a3[3] = {term0, term0, term1}, b3[3] = {pw[0], pw[1], pw[0]}, c3[3] = {acc[0][0], acc[1][0], acc[0][1]};
-            u64 r3[3];
-            gl::mad3(a3, b3, c3, r3);
-            acc[0][0] = r3[0], acc[1][0] = r3[1], acc[0][1] = r3[2];
-            acc[1][1] = gl::mul_add(term1, pw[1], acc[1][1]);
-            pw[0] = r2[1], pw[1] = r2[2];
-            prev[0] = nextv[0], prev[1] = nextv[1];
-        } else {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const u64 term = gl::sub(gl::mul(prev[c], pn[c]), gl::mul(nextv[c], pd[c]));
-                prev[c] = nextv[c];
-#pragma unroll
-                for (int a = 0; a < NC; ++a) acc[a][c] = gl::mul_add(term, pw[a], acc[a][c]);
-            }
-#pragma unroll
-            for (int a = 0; a < NC; ++a) pw[a] = gl::mul(pw[a], q.alphas[a]);
-        }
-    }
-    const u64 zinv = q.zh[((size_t)1 << q.qbits) + r];
-#pragma unroll
-    for (int a = 0; a < NC; ++a) {
-        u64 s = res[a];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) s = gl::mul_add(acc[a][c], q.base[a][c], s);
-        if (q.gate_sums) s = gl::mul_add(q.alpha_k[a], q.gate_sums[(size_t)a * nq + i], s);
-        q.out[(size_t)a * nq + i] = gl::canon(gl::mul(s, zinv));
-    }
+#include "kbody_quotient_perm.hpp"
+}
+// QuotArgs as proof blockIdx.y of M sees them: the member names of QuotArgs, the proof's matrices by their offsets in the table, its beta * k_j
+// rows, gate sums and output NC * num_routed / NC * Nq words behind proof 0's, and the challenges and alpha tables as POINTERS into
+// the table entry -- the body reads them where it uses them, as scalar loads, and nothing per proof sits in a VGPR array
+struct QuotMany {
+    const u64 *wires, *sigmas, *zs;
+    size_t wires_stride, sigmas_stride, zs_stride;
+    const u64 *bk, *zh, *inv_nx1, *gate_sums;
+    u64 *out;
+    unsigned num_routed, degree, num_chunks, log_nq, qbits;
+    const u64 *betas, *gammas, *alphas;
+    const u64 (*base)[4];
+    const u64 *alpha_k;
+    ntt::RootTable roots;
+    __device__ QuotMany(const QuotArgs &s, const ManyProof &t, size_t nc)
+        : wires(s.wires + t.wires_off), sigmas(s.sigmas), zs(s.zs + t.zs_off), wires_stride(t.wires_stride), sigmas_stride(s.sigmas_stride), zs_stride(t.zs_stride),
+          bk(s.bk + blockIdx.y * nc * s.num_routed), zh(s.zh), inv_nx1(s.inv_nx1),
+          gate_sums(s.gate_sums ? s.gate_sums + ((blockIdx.y * nc) << s.log_nq) : nullptr), out(s.out + ((blockIdx.y * nc) << s.log_nq)),
+          num_routed(s.num_routed), degree(s.degree), num_chunks(s.num_chunks), log_nq(s.log_nq), qbits(s.qbits), betas(t.betas), gammas(t.gammas),
+          alphas(t.alphas), base(t.base), alpha_k(t.alpha_k), roots(s.roots) {}
+};
+template <int NC, int DEG>
+__global__ void __launch_bounds__(256) quotient_perm_many_kernel(QuotArgs shared, const ManyProof *__restrict__ tab) {
+    const QuotMany q(shared, tab[blockIdx.y], NC);
+#include "kbody_quotient_perm.hpp"
 }
 
 }  // namespace plonk

@@ -198,6 +198,49 @@ class PolynomialBatch:
         eng.check(rc)
         return cls(eng, h, W, log_n, rate_bits, cap_height, cap)
 
+    @classmethod
+    def from_values_many(cls, values, rate_bits, cap_height, engine=None):
+        """M commitments of one shape in one set of launches (p2hot_commit_many): values [M][W][n] on H_n, M a power of two.
+        Returns M batches that share their device blocks (interleaved columns), each usable wherever a batch is."""
+        return cls._build_many(values, rate_bits, cap_height, True, engine)
+
+    @classmethod
+    def from_coeffs_many(cls, polynomials, rate_bits, cap_height, engine=None):
+        """from_values_many for coefficients [M][W][n]"""
+        return cls._build_many(polynomials, rate_bits, cap_height, False, engine)
+
+    @classmethod
+    def _build_many(cls, cols, rate_bits, cap_height, is_values, engine):
+        eng = engine or default_engine()
+        cols = np.ascontiguousarray(np.asarray(cols, dtype=np.uint64))
+        if cols.ndim != 3:
+            raise ValueError("expected [M][W][n]")
+        M, W, n = cols.shape
+        log_n = int(n).bit_length() - 1
+        if n != 1 << log_n:
+            raise ValueError("polynomial length must be a power of two")
+        ptrs = (C.c_void_p * max(M * W, 1))(*[cols[m, c].ctypes.data for m in range(M) for c in range(W)])
+        caps = np.zeros((M, 1 << cap_height, 4), dtype=np.uint64)
+        hs = (C.c_void_p * max(M, 1))()
+        eng.check(eng.lib.p2hot_commit_many(eng.ctx, ptrs, M, W, log_n, rate_bits, cap_height, 1 if is_values else 0, None, None,
+                                            caps.ctypes.data, hs))
+        return [cls(eng, C.c_void_p(hs[m]), W, log_n, rate_bits, cap_height, caps[m]) for m in range(M)]
+
+    @classmethod
+    def from_device_columns_many(cls, dc, M, rate_bits, cap_height, is_values, engine=None):
+        """p2hot_commit_cols_many: an interleaved set of W * M device columns (column e of proof m is column e * M + m, what the
+        *_many calls of plonk.prover return) -> M batches sharing their blocks.  Consumes `dc` as from_values / from_coeffs do."""
+        eng = engine or dc.engine
+        width, log_n = dc.width, dc.degree_log
+        caps = np.zeros((max(M, 1), 1 << cap_height, 4), dtype=np.uint64)
+        hs = (C.c_void_p * max(M, 1))()
+        handle, dc._h = dc._h, None  # consumed by the library ...
+        rc = eng.lib.p2hot_commit_cols_many(eng.ctx, handle, M, rate_bits, cap_height, 1 if is_values else 0, caps.ctypes.data, hs)
+        if rc in (_lib.EBUSY, _lib.EINVAL) or M == 0:
+            dc._h = handle  # ... except when the call never touched it (both codes, and M = 0, mean "not consumed")
+        eng.check(rc)
+        return [cls(eng, C.c_void_p(hs[m]), width // M, log_n, rate_bits, cap_height, caps[m]) for m in range(M)]
+
     def values(self):
         """the kept input values (keep_values=True) as a borrowed DeviceColumns view"""
         h = C.c_void_p()
@@ -289,6 +332,33 @@ def eval_openings(oracles, points, engine=None):
         cnt = 2 * len(pts) * o._W
         out.append(flat[off:off + cnt].reshape(len(pts), o._W, 2))
         off += cnt
+    return out
+
+
+def eval_openings_many(oracles, points, engine=None):
+    """eval_openings for M proofs in one p2hot_eval_openings_many call: oracles[j] = the oracles of proof j (equally many per
+    proof; the same batch may serve several proofs), points[j] = proof j's extension points [n_points][2].
+    Returns, per proof, the list eval_openings returns."""
+    M = len(oracles)
+    if M == 0:
+        return []
+    eng = engine or oracles[0][0].engine
+    nb = len(oracles[0])
+    if any(len(o) != nb for o in oracles):
+        raise ValueError("every proof opens the same number of oracles")
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(M, -1, 2))
+    npts = pts.shape[1]
+    flat_oracles = [o for per in oracles for o in per]
+    flat = np.zeros(max(1, 2 * npts * sum(o._W for o in flat_oracles)), dtype=np.uint64)
+    eng.check(eng.lib.p2hot_eval_openings_many(eng.ctx, M, _handles(flat_oracles), nb, pts.ctypes.data, npts, flat.ctypes.data))
+    out, off = [], 0
+    for per in oracles:
+        one = []
+        for o in per:
+            cnt = 2 * npts * o._W
+            one.append(flat[off:off + cnt].reshape(npts, o._W, 2))
+            off += cnt
+        out.append(one)
     return out
 
 

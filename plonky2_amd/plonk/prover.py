@@ -334,6 +334,89 @@ def compute_quotient_polys_gates(wires_commitment, constants_sigmas_commitment, 
         a.ctypes.data_as(C.c_void_p), nc, gptrs, gate_set.ptr, vals, h), nc, m, want_values)
 
 
+# ------------------------------------------------------------------ M witnesses of one circuit (include/p2hot.h, the *_many section)
+def _per_proof(v, M, what):
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.uint64))
+    if a.ndim != 2 or a.shape[0] != M:
+        raise ValueError("%s must be [M][num_challenges]" % what)
+    return a
+
+
+def all_wires_permutation_partial_products_many(wires_commitments, sigmas, k_is, quotient_degree_factor, betas, gammas, want_host=False,
+                                                engine=None):
+    """all_wires_permutation_partial_products for M witnesses of one circuit -- one p2hot_partial_products_many call.
+    wires_commitments: the M wires batches (their routed columns are the first len(k_is)); sigmas: DeviceColumns shared by all
+    proofs; betas / gammas [M][num_challenges].  Returns DeviceColumns of rows * M interleaved columns (column e of proof m is
+    column e * M + m) for commit_columns_many, and with want_host also the host array [M][rows][n].  A zero denominator raises
+    ValueError naming the proof."""
+    from ..fri.oracle import DeviceColumns, _handles
+    M = len(wires_commitments)
+    eng = engine or sigmas.engine
+    k = np.ascontiguousarray(np.asarray(k_is, dtype=np.uint64))
+    b, g = _per_proof(betas, M, "betas"), _per_proof(gammas, M, "gammas")
+    if b.shape != g.shape:
+        raise ValueError("betas and gammas must have one shape")
+    nc = b.shape[1]
+    out = None
+    if want_host and M:
+        rows = nc * (num_partial_products(len(k), quotient_degree_factor) + 1)
+        out = np.zeros((M, rows, 1 << sigmas.degree_log), dtype=np.uint64)
+    h = C.c_void_p()
+    rc = eng.lib.p2hot_partial_products_many(eng.ctx, M, _handles(wires_commitments), 0, sigmas._h, 0, k.ctypes.data_as(C.c_void_p), len(k),
+                                             quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), nc,
+                                             out.ctypes.data_as(C.c_void_p) if out is not None else None, C.byref(h))
+    if rc == 1 and b"tried to invert zero" in eng.lib.p2hot_last_error(eng._ctx):
+        raise ValueError(eng.lib.p2hot_last_error(eng._ctx).decode())  # the reference panics (field/src/types.rs:133)
+    eng.check(rc)
+    cols = DeviceColumns(eng, h)
+    return (cols, out) if want_host else cols
+
+
+def commit_columns_many(cols, M, rate_bits, cap_height, is_values, engine=None):
+    """p2hot_commit_cols_many: the interleaved DeviceColumns of a *_many call -> M PolynomialBatch sharing their blocks"""
+    from ..fri.oracle import PolynomialBatch
+    return PolynomialBatch.from_device_columns_many(cols, M, rate_bits, cap_height, is_values, engine=engine)
+
+
+def compute_quotient_polys_gates_many(wires_commitments, constants_sigmas_commitment, sigmas_first_col, zs_partial_products_commitments,
+                                      k_is, quotient_degree_factor, betas, gammas, alphas, gate_set=None, public_inputs_hashes=None,
+                                      want_values=False, want_chunks=True, engine=None):
+    """compute_quotient_polys_gates for M witnesses of one circuit -- one p2hot_quotient_polys_gates_many call.  betas / gammas /
+    alphas [M][num_challenges]; public_inputs_hashes [M][4] or None (the set's for every proof); gate_set None: permutation terms
+    only.  Returns the chunks as interleaved DeviceColumns (nc * quotient_degree_factor * M columns) for commit_columns_many, the
+    values [M][nc][n << qbits] with want_values (alone with want_chunks=False).  "Quotient has failed" raises ValueError naming
+    the proof."""
+    from ..fri.oracle import DeviceColumns, _handles
+    M = len(wires_commitments)
+    eng = engine or constants_sigmas_commitment.engine
+    k = np.ascontiguousarray(np.asarray(k_is, dtype=np.uint64))
+    b, g, a = _per_proof(betas, M, "betas"), _per_proof(gammas, M, "gammas"), _per_proof(alphas, M, "alphas")
+    if not b.shape == g.shape == a.shape:
+        raise ValueError("betas, gammas and alphas must have one shape")
+    nc = b.shape[1]
+    pih = None
+    if public_inputs_hashes is not None:
+        pih = np.ascontiguousarray(np.asarray(public_inputs_hashes, dtype=np.uint64))
+        if pih.shape != (M, 4):
+            raise ValueError("public_inputs_hashes must be [M][4]")
+    m = (1 << constants_sigmas_commitment.degree_log) << max(0, (quotient_degree_factor - 1).bit_length())
+    vals = np.zeros((M, nc, m), dtype=np.uint64) if want_values else None
+    h = C.c_void_p()
+    rc = eng.lib.p2hot_quotient_polys_gates_many(
+        eng.ctx, M, _handles(wires_commitments), constants_sigmas_commitment._h, sigmas_first_col, _handles(zs_partial_products_commitments),
+        k.ctypes.data_as(C.c_void_p), len(k), quotient_degree_factor, b.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+        a.ctypes.data_as(C.c_void_p), nc, gate_set.ptr if gate_set is not None else None,
+        pih.ctypes.data_as(C.c_void_p) if pih is not None else None, vals.ctypes.data_as(C.c_void_p) if want_values else None,
+        C.byref(h) if want_chunks else None)
+    if rc == 1 and b"Quotient has failed" in eng.lib.p2hot_last_error(eng._ctx):
+        raise ValueError(eng.lib.p2hot_last_error(eng._ctx).decode())  # the reference panics (polynomial/mod.rs:164-178)
+    eng.check(rc)
+    if not want_chunks:
+        return vals
+    cols = DeviceColumns(eng, h)
+    return (cols, vals) if want_values else cols
+
+
 def compute_quotient_polys_lookup_gates(wires_commitment, constants_sigmas_commitment, sigmas_first_col,
                                         zs_partial_products_lookups_commitment, k_is, quotient_degree_factor, betas, gammas, alphas,
                                         num_lu_slots, num_lut_slots, lookup_selectors_first_col, deltas, lut_re_poly_evals, gate_set,
