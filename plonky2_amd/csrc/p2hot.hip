@@ -1948,6 +1948,68 @@ extern "C" int p2hot_eval_polys_dev(p2hot_ctx *ctx, const uint64_t *const *d_pol
     return P2HOT_OK;
 }
 
+// The plan of the prefix-product scan for M proofs of one shape whose rows lie back to back (M = 1: p2hot_partial_products_dev), and
+// its scratch: 2 x (chunk denominators [M][num_chunks][n] | row totals [M][n]) | chunk products [M][n_chunks] | carries | flags [M]
+// (two sets: a pair of challenges goes through pp_quotients2_kernel in one pass)
+struct PPPlan {
+    size_t M;
+    unsigned num_routed, degree, log_n, nc;
+    size_t n = (size_t)1 << log_n;
+    unsigned num_chunks = (num_routed + degree - 1) / degree, num_prods = num_chunks - 1, chunk_log = log_n < 6 ? log_n : 6;  // rows per scan chunk
+    size_t n_chunks = n >> chunk_log, per = (n_chunks + 1023) / 1024, set_words = M * ((size_t)num_chunks * n + n);
+    u64 *sets = nullptr, *prod = nullptr, *carry = nullptr;
+    unsigned *flags = nullptr;
+    size_t scratch_words() const { return 2 * set_words + 2 * M * n_chunks + M; }
+    void carve(u64 *scratch) { sets = scratch, prod = sets + 2 * set_words, carry = prod + M * n_chunks, flags = (unsigned *)(carry + M * n_chunks); }
+};
+
+// one PPArgs per challenge: proof 0's blocks (the M-form kernels step to proof blockIdx.y).  The output is [nc Zs | nc * num_prods
+// partial products] columns of out_stride words; betas == NULL: the kernels take (beta, gamma) from the per-proof table
+static std::vector<plonk::PPArgs> pp_args(p2hot_ctx *ctx, const PPPlan &pl, const u64 *d_wires, size_t wires_stride, const u64 *d_sigmas,
+                                          size_t sigmas_stride, const u64 *d_k, const uint64_t *betas, const uint64_t *gammas, u64 *d_out,
+                                          size_t out_stride) {
+    std::vector<plonk::PPArgs> args(pl.nc);
+    for (unsigned ch = 0; ch < pl.nc; ++ch) {
+        plonk::PPArgs &a = args[ch];
+        a.wires = d_wires, a.wires_stride = wires_stride, a.sigmas = d_sigmas, a.sigmas_stride = sigmas_stride, a.k_is = d_k;
+        a.num_routed = pl.num_routed, a.degree = pl.degree, a.num_chunks = pl.num_chunks, a.log_n = pl.log_n;
+        a.beta = betas ? gl::canon(betas[ch]) : 0, a.gamma = betas ? gl::canon(gammas[ch]) : 0;
+        a.roots = ctx->fwd;
+        a.pp = d_out + ((size_t)pl.nc + (size_t)ch * pl.num_prods) * out_stride, a.pp_stride = out_stride;
+        a.dchunk = pl.sets + (size_t)(ch & 1) * pl.set_words, a.total = a.dchunk + pl.M * (size_t)pl.num_chunks * pl.n;
+        a.zero_flag = pl.flags;
+    }
+    return args;
+}
+
+// per challenge: quotients -> chunk totals -> carries -> emit Z -> scale.  d_tab (p2hot_partial_products_many): the M-form quotient
+// and carry kernels, one grid row per proof; the proofs' rows lie back to back, so the chunk totals, the Z walk and the scaling run
+// over M * n rows either way and only the carries restart per proof
+static int pp_launch(p2hot_ctx *ctx, const PPPlan &pl, const std::vector<plonk::PPArgs> &args, u64 *d_out, size_t out_stride,
+                     const plonk::ManyProof *d_tab) {
+    const size_t rows = pl.M * pl.n, chunks = pl.M * pl.n_chunks, wires_step = (size_t)pl.num_routed * pl.n;
+    const dim3 grid(cdiv(pl.n, 256), (unsigned)pl.M), b256(256), b1024(1024);
+    for (unsigned ch = 0; ch < pl.nc; ++ch) {
+        const plonk::PPArgs &a = args[ch];
+        u64 *z = d_out + (size_t)ch * out_stride;
+        if (ctx->pp_streams && (ch & 1) == 0 && ch + 1 < pl.nc) {  // a pair of challenges: one pass over the wires and sigmas
+            plonk::PPArgs2 two{{args[ch], args[ch + 1]}};
+            if (d_tab) P2HOT_LAUNCH(plonk::pp_quotients2_many_kernel, grid, b256, 0, ctx->stream, two, d_tab, ch, wires_step);
+            else P2HOT_LAUNCH(plonk::pp_quotients2_kernel, grid, b256, 0, ctx->stream, two);
+        } else if (!(ctx->pp_streams && (ch & 1))) {
+            if (d_tab) P2HOT_LAUNCH(plonk::pp_quotients_many_kernel, grid, b256, 0, ctx->stream, a, d_tab, ch, wires_step);
+            else P2HOT_LAUNCH(plonk::pp_quotients_kernel, grid, b256, 0, ctx->stream, a);
+        }
+        P2HOT_LAUNCH(plonk::pp_chunk_totals_kernel, dim3(cdiv(chunks, 256)), b256, 0, ctx->stream, (const u64 *)a.total, pl.chunk_log, chunks, pl.prod);
+        if (d_tab) P2HOT_LAUNCH(plonk::pp_carries_many_kernel, dim3(1, (unsigned)pl.M), b1024, 0, ctx->stream, (const u64 *)pl.prod, pl.n_chunks, pl.per, pl.carry);
+        else P2HOT_LAUNCH(plonk::pp_carries_kernel, dim3(1), b1024, 0, ctx->stream, (const u64 *)pl.prod, pl.n_chunks, pl.per, pl.carry);
+        P2HOT_LAUNCH(plonk::pp_emit_z_kernel, dim3(cdiv(chunks, 256)), b256, 0, ctx->stream, (const u64 *)a.total, pl.chunk_log, chunks, (const u64 *)pl.carry, z);
+        if (pl.num_prods) P2HOT_LAUNCH(plonk::pp_scale_kernel, dim3(cdiv(rows, 256)), b256, 0, ctx->stream, a.pp, out_stride, pl.num_prods, (const u64 *)z, rows);
+        P2_LAUNCH_CHECK(ctx);
+    }
+    return P2HOT_OK;
+}
+
 extern "C" int p2hot_partial_products_dev(p2hot_ctx *ctx, const uint64_t *d_wires, size_t wires_stride,
                                           const uint64_t *d_sigmas, size_t sigmas_stride, const uint64_t *k_is,
                                           unsigned num_routed, unsigned log_n, unsigned degree, const uint64_t *betas,
@@ -1962,66 +2024,19 @@ extern "C" int p2hot_partial_products_dev(p2hot_ctx *ctx, const uint64_t *d_wire
     if (!d_wires || !d_sigmas || !k_is || !betas || !gammas || !d_out)
         P2_FAIL(ctx, P2HOT_EINVAL, "partial_products: null argument");
     if (wires_stride < n || sigmas_stride < n || out_stride < n) P2_FAIL(ctx, P2HOT_EINVAL, "partial_products: stride < n");
-    const unsigned num_chunks = (num_routed + degree - 1) / degree, num_prods = num_chunks - 1;
-    const unsigned chunk_log = log_n < 6 ? log_n : 6;  // rows per scan chunk
-    const size_t n_chunks = n >> chunk_log, per = (n_chunks + 1023) / 1024;
-    // scratch: k_is | 2 x (chunk denominators [num_chunks][n] | row totals [n]) | chunk products | carries | flag
-    // (two sets: a pair of challenges goes through pp_quotients2_kernel in one pass)
-    const size_t set_words = (size_t)num_chunks * n + n;
-    const size_t words = num_routed + 2 * set_words + 2 * n_chunks + 1;
-    u64 *base = nullptr;
-    P2_TRY(scratch_get(ctx, 0, words * 8, (void **)&base));
-    u64 *d_k = base, *sets = d_k + num_routed, *prod = sets + 2 * set_words, *carry = prod + n_chunks;
-    unsigned *flag = (unsigned *)(carry + n_chunks);
+    PPPlan pl{1, num_routed, degree, log_n, num_challenges};
+    u64 *d_k = nullptr;  // scratch: k_is | the plan's
+    P2_TRY(scratch_get(ctx, 0, (num_routed + pl.scratch_words()) * 8, (void **)&d_k));
+    pl.carve(d_k + num_routed);
     std::vector<u64> kc(num_routed);
     for (unsigned j = 0; j < num_routed; ++j) kc[j] = gl::canon(k_is[j]);
     P2_HIP(ctx, hipMemcpyAsync(d_k, kc.data(), (size_t)num_routed * 8, hipMemcpyHostToDevice, ctx->stream));
-    P2_HIP(ctx, hipMemsetAsync(flag, 0, 8, ctx->stream));
+    P2_HIP(ctx, hipMemsetAsync(pl.flags, 0, 8, ctx->stream));
     ProfScope ps(ctx, "partial_products");
-    std::vector<plonk::PPArgs> args(num_challenges);
-    for (unsigned ch = 0; ch < num_challenges; ++ch) {
-        plonk::PPArgs &a = args[ch];
-        u64 *dchunk = sets + (size_t)(ch & 1) * set_words, *total = dchunk + (size_t)num_chunks * n;
-        a.wires = d_wires;
-        a.sigmas = d_sigmas;
-        a.wires_stride = wires_stride;
-        a.sigmas_stride = sigmas_stride;
-        a.k_is = d_k;
-        a.num_routed = num_routed;
-        a.degree = degree;
-        a.num_chunks = num_chunks;
-        a.log_n = log_n;
-        a.beta = gl::canon(betas[ch]);
-        a.gamma = gl::canon(gammas[ch]);
-        a.roots = ctx->fwd;
-        a.pp = d_out + ((size_t)num_challenges + (size_t)ch * num_prods) * out_stride;
-        a.pp_stride = out_stride;
-        a.dchunk = dchunk;
-        a.total = total;
-        a.zero_flag = flag;
-    }
-    for (unsigned ch = 0; ch < num_challenges; ++ch) {
-        const plonk::PPArgs &a = args[ch];
-        const u64 *total = a.total;
-        u64 *z = d_out + (size_t)ch * out_stride;
-        if (ctx->pp_streams && (ch & 1) == 0 && ch + 1 < num_challenges) {  // a pair of challenges: one pass over the wires and sigmas
-            plonk::PPArgs2 two{{args[ch], args[ch + 1]}};
-            P2HOT_LAUNCH(plonk::pp_quotients2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, two);
-        } else if (!(ctx->pp_streams && (ch & 1))) {
-            P2HOT_LAUNCH(plonk::pp_quotients_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, a);
-        }
-        P2HOT_LAUNCH(plonk::pp_chunk_totals_kernel, dim3(cdiv(n_chunks, 256)), dim3(256), 0, ctx->stream, (const u64 *)total,
-                     chunk_log, n_chunks, prod);
-        P2HOT_LAUNCH(plonk::pp_carries_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const u64 *)prod, n_chunks, per, carry);
-        P2HOT_LAUNCH(plonk::pp_emit_z_kernel, dim3(cdiv(n_chunks, 256)), dim3(256), 0, ctx->stream, (const u64 *)total,
-                     chunk_log, n_chunks, (const u64 *)carry, z);
-        if (num_prods)
-            P2HOT_LAUNCH(plonk::pp_scale_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, a.pp, out_stride, num_prods,
-                         (const u64 *)z, n);
-        P2_LAUNCH_CHECK(ctx);
-    }
+    P2_TRY(pp_launch(ctx, pl, pp_args(ctx, pl, d_wires, wires_stride, d_sigmas, sigmas_stride, d_k, betas, gammas, d_out, out_stride), d_out, out_stride,
+                     nullptr));
     unsigned zero = 0;
-    P2_HIP(ctx, hipMemcpyAsync(&zero, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    P2_HIP(ctx, hipMemcpyAsync(&zero, pl.flags, 4, hipMemcpyDeviceToHost, ctx->stream));
     P2_HIP(ctx, stream_sync(ctx));
     if (zero) P2_FAIL(ctx, P2HOT_EINVAL, "partial_products: tried to invert zero (a denominator wire + beta*sigma + gamma vanished)");
     return P2HOT_OK;
@@ -2160,6 +2175,7 @@ struct p2hot_cols {
 };
 
 #include "host_prover.hpp"
+#include "host_plonk.hpp"
 #include "host_air.hpp"
 #include "host_stark.hpp"
 #include "host_multi.hpp"

@@ -166,7 +166,7 @@ def test_lookup_polys_vs_restatement(eng, num_routed, lookup_degree, log_n, nc, 
 
 def _carries_per(region):
     """chunks per thread of lookup::lookup_carries_kernel for one region: SCAN_CHUNK = 4 rows per chunk (csrc/lookup.hpp), one block
-    of 1024 threads over the chunks (its launch in p2hot_lookup_polys, csrc/host_prover.hpp)"""
+    of 1024 threads over the chunks (its launch in p2hot_lookup_polys, csrc/host_plonk.hpp)"""
     last_lu, _, first_lut = region
     n_chunks = lr.div_ceil(first_lut - last_lu + 1, 4)
     return n_chunks, lr.div_ceil(n_chunks, 1024)

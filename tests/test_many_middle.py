@@ -5,7 +5,8 @@ The yardstick is the single-proof path, which tests/test_vanishing_identity.py, 
 restatements (vanishing_ref.py, gates_ref.py, recursion_gates_ref.py): every result of an M-form must equal M single-proof calls word
 for word.  Sizes: 2^5 rows (one scan chunk per proof) and 2^7 (two), rate 3, cap 2; nc 2 with degree 8 (the pipelined quotient
 instantiation) and nc 3 with degree 4 (the generic one); the recursion gate set needs factor 8 (and 7 for a quotient whose trim
-can fail), so the gate cases run nc 2 and nc 3 at those."""
+can fail), so the gate cases run nc 2 and nc 3 at those.  nc 1 and nc 4 at 2^5 rows and M = 2 run the remaining instantiations of
+the quotient and gate M-forms and the partial products' pairing rule with a lone challenge and with two pairs."""
 import ctypes as C
 
 import numpy as np
@@ -48,7 +49,7 @@ def _commit_wires(eng, wires, shared, rate_bits=RATE_BITS):
 
 # ------------------------------------------------------------------ 1. partial products and Zs
 PP_CASES = [(5, 2, 8, 1, True), (5, 2, 8, 2, False), (5, 2, 8, 8, True), (5, 3, 4, 1, False), (5, 3, 4, 2, True), (5, 3, 4, 8, False),
-            (7, 2, 8, 2, True), (7, 2, 8, 8, False), (7, 3, 4, 2, False), (7, 3, 4, 8, True)]
+            (7, 2, 8, 2, True), (7, 2, 8, 8, False), (7, 3, 4, 2, False), (7, 3, 4, 8, True), (5, 1, 4, 2, True), (5, 4, 4, 2, False)]
 
 
 @pytest.mark.parametrize("log_n,nc,degree,M,shared", PP_CASES)
@@ -217,7 +218,8 @@ def _single_quotient(eng, circ, bw, bcs, bz, ch, m, pih, gates=True):
 
 
 # ------------------------------------------------------------------ 3. the quotient with the recursion gate set
-@pytest.mark.parametrize("log_n,nc,M,shared", [(5, 2, 2, True), (5, 3, 2, False), (7, 2, 2, False), (5, 2, 8, True), (5, 2, 1, False)])
+@pytest.mark.parametrize("log_n,nc,M,shared", [(5, 2, 2, True), (5, 3, 2, False), (7, 2, 2, False), (5, 2, 8, True), (5, 2, 1, False),
+                                                 (5, 1, 2, False), (5, 4, 2, True)])
 def test_quotient_polys_gates_many_equals_single_calls(eng, log_n, nc, M, shared):
     """satisfied witnesses, per-proof challenges and public-inputs hashes: values and interleaved chunks equal M
     p2hot_quotient_polys_gates calls bit for bit; one proof's chunks pass the verifier's identity at an extension point"""
@@ -239,7 +241,7 @@ def test_quotient_polys_gates_many_equals_single_calls(eng, log_n, nc, M, shared
     assert trg._identity_holds(eng, q, {"cs": bcs, "wires": bw[m], "zs": bz[m]}, inter[:, m], nc, 3) == [True] * nc
 
 
-@pytest.mark.parametrize("log_n,nc,qdf", [(5, 3, 4), (7, 2, 8)])
+@pytest.mark.parametrize("log_n,nc,qdf", [(5, 3, 4), (7, 2, 8), (5, 1, 4), (5, 4, 4)])
 def test_quotient_many_without_gates_equals_quotient_polys(eng, log_n, nc, qdf):
     """gates = NULL: the permutation terms only, p2hot_quotient_polys with no gate sums (random columns: the quotient need not be a
     polynomial where the factor keeps every coefficient)"""

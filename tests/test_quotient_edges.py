@@ -1,5 +1,5 @@
 """The gate kernels of the quotient (gates::cheap_gates_kernel, gates::poseidon_gate_kernel, the launches of gates_launch in
-csrc/host_prover.hpp) at the edges tests/test_gates.py leaves out: more cheap descriptors than one launch carries, operands from
+csrc/host_plonk.hpp) at the edges tests/test_gates.py leaves out: more cheap descriptors than one launch carries, operands from
 the field's edge grid, alphas handed over as alpha + P, a quotient step above 1, a blinded and a Keccak-hashed commitment.  Every
 comparison is bit for bit with tests/gates_ref.py over tests/vanishing_ref.py's LDE rows; the helpers are tests/test_gates.py's."""
 import numpy as np
