@@ -29,12 +29,12 @@ ROWS = [
     ("e", "multi-GPU", "test_distributed.py (gloo 2/4/8), test_emu_rccl_ranks.py, test_emu_devices.py, test_bench_launch.py (`bench.py --gpus 2` self-launched, incl. the per-proof path over the group), test_gpu_fullsize.py (C5 as 8 ranks on one GPU; the k20 proof over a group of 2 / 8 ranks; RCCL bound with and without torch)", "multi"),
     ("f1", "prove_openings prelude", "test_prove_openings.py::test_final_poly_and_prove_openings_vs_oracle; test_gpu_fullsize.py::test_proof_path_full_size_vs_oracle_records_and_verifier", "path"),
     ("f2", "PoW + query phase", "test_prove_openings.py::test_fri_proof_passes_the_reference_verifier; full size: the k20 / starky k22 FriProof bytes = the oracle's, verified + 6 tamperings", "path"),
-    ("f3", "partial products / Z, quotient permutation terms, OpeningSet", "test_permutation.py; test_vanishing_identity.py (Zs and quotient vs tests/vanishing_ref.py, a restatement of the reference; the device quotient through verifier.rs:83-98 at an extension point); full size: SHA-256 of the Zs matrix, the 2^23 quotient values, the 16 chunks, all 275 openings vs the oracle record; gate sums on 4096 points + linearity", "path"),
+    ("f3", "partial products / Z, quotient permutation terms, OpeningSet", "test_permutation.py; test_vanishing_identity.py (Zs and quotient vs tests/vanishing_ref.py, a restatement of the reference; the device quotient through verifier.rs:83-98 at an extension point); full size: SHA-256 of the Zs matrix, the 2^23 quotient values, the 16 chunks, all 275 openings vs the oracle record; gate sums on 4096 points + linearity; test_edge_words.py (the quotient's permutation, gate and Plonk-lookup terms, the partial products, final_poly and the openings on edge words, a different one in every lane, vs Python integers row by row)", "path"),
     ("f4", "wire formats", "tests/wire_format.py checker; the FriProof bytes of the full-size proofs hash to the oracle's; test_gpu_fullsize.py::test_polynomial_batch_wire_bytes_vs_oracle_at_full_size (SHA-256 of the whole write_polynomial_batch stream, C2 wires + C3 quotient chunks); Rust serializer: never compiled", None),
-    ("f5", "starky lookups and cross-table lookups: auxiliary polynomials, their terms of the quotient", "test_stark_lookup.py (every stage vs tests/stark_lookup_ref.py, a restatement of starky's lookup.rs / cross_table_lookup.rs / compute_quotient_polys; divisibility; the device quotient through starky's verifier.rs:167-186 at an extension point; every error), test_stark_lookup_ref.py (the restatement's own properties), test_stark_lookup_codeobj.py", None),
-    ("f6", "a STARK's own constraints from a constraint program: the consumer's accumulators, the table's whole quotient", "test_stark_air.py (the builder; the accumulators point by point vs tests/stark_air_ref.py, constraint functions restated from starky's fibonacci_stark.rs and a synthetic AIR, plus an independent interpreter of the program format; fused = two-step bit for bit; FibonacciStark's quotient through verifier.rs:167-186 at an extension point; divisibility; the temp cap; every error), test_stark_air_codeobj.py", None),
-    ("f7", "user-defined gates' constraints from gate programs: the reduced sums, the plonk quotient with and without lookups", "test_gate_program.py (the builder; nine reference gates transcribed for it vs the hand-written kinds and tests/gates_ref.py bit for bit; a gate the library does not know vs tests/gate_program_ref.py, an independent interpreter of the format, and vs a plain function; a mixed call vs the reference sum and vs the host residual; the device quotient through verifier.rs:83-98; a broken wire; every error; Keccak-hashed commitments), test_gate_program_codeobj.py", None),
-    ("f8", "the middle of a proof for M witnesses of one circuit: partial products and Zs, commitment of interleaved device columns, quotient with gate constraints, OpeningSet", "test_many_middle.py (every M-form vs M single-proof calls word for word: handles sharing one block and separately committed ones, one and two scan chunks, the pipelined and the generic quotient instantiation, per-proof challenges and public-inputs hashes; one proof's chunks through verifier.rs:83-98; a zero denominator and a broken wire name their proof; the whole chain for M = 4 up to the opening proofs' bytes; every argument error), test_many_middle_codeobj.py", None),
+    ("f5", "starky lookups and cross-table lookups: auxiliary polynomials, their terms of the quotient", "test_stark_lookup.py (every stage vs tests/stark_lookup_ref.py, a restatement of starky's lookup.rs / cross_table_lookup.rs / compute_quotient_polys; divisibility; the device quotient through starky's verifier.rs:167-186 at an extension point; every error), test_stark_lookup_ref.py (the restatement's own properties), test_stark_lookup_codeobj.py, test_edge_words.py (edge traces and wrapped edge matrices)", None),
+    ("f6", "a STARK's own constraints from a constraint program: the consumer's accumulators, the table's whole quotient", "test_stark_air.py (the builder; the accumulators point by point vs tests/stark_air_ref.py, constraint functions restated from starky's fibonacci_stark.rs and a synthetic AIR, plus an independent interpreter of the program format; fused = two-step bit for bit; FibonacciStark's quotient through verifier.rs:167-186 at an extension point; divisibility; the temp cap; every error), test_stark_air_codeobj.py, test_edge_words.py (a program whose temps leave [0, P), on edge traces)", None),
+    ("f7", "user-defined gates' constraints from gate programs: the reduced sums, the plonk quotient with and without lookups", "test_gate_program.py (the builder; nine reference gates transcribed for it vs the hand-written kinds and tests/gates_ref.py bit for bit; a gate the library does not know vs tests/gate_program_ref.py, an independent interpreter of the format, and vs a plain function; a mixed call vs the reference sum and vs the host residual; the device quotient through verifier.rs:83-98; a broken wire; every error; Keccak-hashed commitments), test_gate_program_codeobj.py, test_edge_words.py (a program whose temps leave [0, P), on edge rows)", None),
+    ("f8", "the middle of a proof for M witnesses of one circuit: partial products and Zs, commitment of interleaved device columns, quotient with gate constraints, OpeningSet", "test_many_middle.py (every M-form vs M single-proof calls word for word: handles sharing one block and separately committed ones, one and two scan chunks, the pipelined and the generic quotient instantiation, per-proof challenges and public-inputs hashes; one proof's chunks through verifier.rs:83-98; a zero denominator and a broken wire name their proof; the whole chain for M = 4 up to the opening proofs' bytes; every argument error), test_many_middle_codeobj.py, test_edge_words.py (an edge proof between two random ones)", None),
     ("g1", "patched CircuitBuilder::build / prove vs the Rust prover", "integration/first_contact.sh (dry-run only: no cargo in the image)", None),
 ]
 
