@@ -268,6 +268,32 @@ int p2hot_merkle_paths_dev(p2hot_ctx *ctx, const uint64_t *d_digests, unsigned l
  * (the reference's rayon find_any returns an arbitrary valid one), observes it and draws the
  * response like the reference does.  The candidates go through the challenger's permutation (Poseidon or KeccakPermutation). */
 int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsigned pow_bits, uint64_t *witness_out);
+/* fri_committed_trees (fri/prover.rs:84-150) for M final polynomials of ONE shape in one set of launches: the M-form of
+ * p2hot_fri_commit_dev.  Per round the M codewords are the 2M columns of one coset LDE (prover.rs:119, fri/oracle.rs:215-220), the
+ * M round trees one forest of M << cap_height cap subtrees (prover.rs:99-104: proof j's digests and cap are contiguous and in the
+ * single tree's layout), and one launch observes cap j and draws beta j for every transcript (prover.rs:106-109), one folds
+ * (prover.rs:111-118).  The dummy caps of max_num_query_steps, the final polynomials and the zero padding to final_poly_coeff_len
+ * (prover.rs:122-147) are observed by every transcript in one launch each.
+ *   d_coeffs_planar  DEVICE planes [2][M][n]: component c of proof j's coefficients at (c * M + j) * n
+ *   challengers      M distinct Poseidon transcripts of this context; transcript j is advanced exactly as p2hot_fri_commit_dev
+ *                    advances it for proof j alone (the transcripts may hold different numbers of buffered elements)
+ *   outputs (any may be NULL) are PROOF-MAJOR: proof j's block is what p2hot_fri_commit_dev writes for it, the blocks back to back
+ *     d_leaves_out   DEVICE [M][leaf words], digests_out DEVICE (digests_on_device != 0) or host [M][digest words],
+ *     caps_out       host [M][n_rounds][4 << cap_height], betas_out host [M][n_rounds][2], final_out host [M][n_final][2]
+ * Every word equals M p2hot_fri_commit_dev calls'.  A call is split into groups of proofs so that the round scratch stays bounded
+ * (M_group << (log_n + rate_bits) <= 2^22 extension elements; P2HOT_MANY_GROUP, read per call, lowers the proofs per group).
+ * A Keccak transcript is P2HOT_EUNSUPPORTED (one at a time: p2hot_fri_commit_dev); everything is validated before the first enqueue. */
+int p2hot_fri_commit_many_dev(p2hot_ctx *ctx, size_t M, const uint64_t *d_coeffs_planar, unsigned log_n, unsigned rate_bits,
+                              unsigned cap_height, const unsigned *arity_bits, unsigned n_rounds, unsigned max_num_query_steps,
+                              size_t final_poly_coeff_len, p2hot_challenger *const *challengers, uint64_t *d_leaves_out,
+                              uint64_t *digests_out, int digests_on_device, uint64_t *caps_out, uint64_t *betas_out,
+                              uint64_t *final_out);
+/* fri_proof_of_work (fri/prover.rs:153-202) for M transcripts in one set of launches: the M-form of p2hot_fri_pow.  The candidate
+ * chunks are shared by all proofs (grid: blocks x M) and a block of proof j retires at once when witness j is known; witnesses_out[j]
+ * is the SMALLEST valid witness of transcript j, which then observes it and draws the response (prover.rs:197-198), as
+ * p2hot_fri_pow does.  A transcript whose device-searched range holds no witness continues alone with host-checked chunks.
+ * Keccak transcripts: P2HOT_EUNSUPPORTED. */
+int p2hot_fri_pow_many(p2hot_ctx *ctx, size_t M, p2hot_challenger *const *challengers, unsigned pow_bits, uint64_t *witnesses_out);
 
 /* ================================================================ prover session (HOST pointers)
  * What the patched plonky2 crate calls from the prover's main thread with ordinary Vec<F> buffers.  Everything between
@@ -481,11 +507,25 @@ int p2hot_fri_proof_sizes(const p2hot_batch *const *oracles, size_t n_oracles, c
 int p2hot_prove_openings(p2hot_ctx *ctx, const p2hot_fri_batch_info *batches, size_t n_batches,
                          const p2hot_batch *const *oracles, size_t n_oracles, p2hot_challenger *challenger,
                          const p2hot_fri_params *params, p2hot_fri_proof *proof);
-/* M independent opening proofs side by side (recursion workloads: many 2^12-row proofs, each a latency-bound chain of small
+/* M independent opening proofs per call (recursion workloads: many 2^12-row proofs, each a latency-bound chain of small
  * launches).  Proof j opens oracles[j * n_oracles .. + n_oracles) (handles of THIS context, e.g. from p2hot_commit_many) at
  * batches[j][0 .. n_batches[j]) with transcript challengers[j] and fills proofs[j]; every proof is computed exactly as by
- * p2hot_prove_openings (same buffers, same transcript afterwards).  Inside, up to 4 sibling contexts of the same GPU --
- * own streams, driven by their own host threads -- run the proofs concurrently. */
+ * p2hot_prove_openings (same buffers, same transcript afterwards).  Two paths, equal byte for byte:
+ *   fused         Proofs of ONE SHAPE share every launch, on the caller's context and stream, with no helper threads: alpha_j and the
+ *                 final polynomials (fri/oracle.rs:186-213) as planes [2][M][n], the commit phase as p2hot_fri_commit_many_dev runs
+ *                 it (fri/prover.rs:84-150: per round one LDE of 2M columns, one forest, one transcript launch, one fold), the grind
+ *                 as p2hot_fri_pow_many (prover.rs:153-202), then the query rounds (prover.rs:204-258) of the M oracles of each oracle
+ *                 position and of the M round trees of each round, written in the proof layout above into one staging block that
+ *                 one copy brings back.  Everything is validated before the first enqueue (a per-proof message names the proof)
+ *                 and the call synchronises once.  A call is split into groups of proofs (p2hot_fri_commit_many_dev's bound).  A proof
+ *                 whose device-searched grind range held no witness gets its transcript back and is proved again alone.
+ *                 One shape: distinct transcripts; the same n_batches[j]; the same (oracle_index, poly_index) lists in every batch
+ *                 (the points are per proof); the same polynomial and salt widths per oracle position.  The handles may be shares of
+ *                 one p2hot_commit_many block or separately committed, in any mixture.
+ *   side by side  Anything else, and every call under P2HOT_MANY_FUSED=0 (read per call): up to 4 sibling contexts of the same GPU --
+ *                 own streams, driven by their own host threads -- run M single-proof chains concurrently.
+ * Measured at the recursion shape the fused path wins from M = 1 on, so every eligible call takes it.
+ * Keccak transcripts or oracles: P2HOT_EUNSUPPORTED on both paths. */
 int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_fri_batch_info *const *batches, const size_t *n_batches,
                               const p2hot_batch *const *oracles, size_t n_oracles, p2hot_challenger *const *challengers,
                               const p2hot_fri_params *fp, p2hot_fri_proof *proofs);
@@ -678,7 +718,7 @@ int p2hot_quotient_polys_lookup_gates(p2hot_ctx *ctx, const p2hot_batch *wires, 
  * proofs of different degree or rate; a per-proof message names the proof), M == 0 is P2HOT_OK with nothing done, numeric
  * failures found on the device use one flag word per proof, and each call synchronises the host once.
  * NOT in the M-form, left to the single-proof entry points: the host gate_sums residual, lookups and gate programs; Keccak trees in
- * p2hot_commit_cols_many; the multi-GPU group; and p2hot_prove_openings_many still runs its proofs side by side, not batched. */
+ * p2hot_commit_cols_many; the multi-GPU group.  (p2hot_prove_openings_many batches proofs of one shape in the same way.) */
 
 /* all_wires_permutation_partial_products for M witnesses of one circuit.  wires[m]: the wires commitment of proof m (any
  * handle of this context, e.g. from p2hot_commit_many); the routed wires' VALUES on H are recomputed on the device from its

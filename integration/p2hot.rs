@@ -447,6 +447,15 @@ extern "C" {
         ctx: *mut P2hotCtx, d_digests: *const u64, log_leaves: c_uint, cap_height: c_uint, d_idx: *const u64, m: usize, d_out: *mut u64,
     ) -> c_int;
     pub fn p2hot_fri_pow(ctx: *mut P2hotCtx, challenger: *mut P2hotChallenger, pow_bits: c_uint, witness_out: *mut u64) -> c_int;
+    pub fn p2hot_fri_commit_many_dev(
+        ctx: *mut P2hotCtx, M: usize, d_coeffs_planar: *const u64, log_n: c_uint, rate_bits: c_uint, cap_height: c_uint,
+        arity_bits: *const c_uint, n_rounds: c_uint, max_num_query_steps: c_uint, final_poly_coeff_len: usize,
+        challengers: *const *mut P2hotChallenger, d_leaves_out: *mut u64, digests_out: *mut u64, digests_on_device: c_int, caps_out: *mut u64,
+        betas_out: *mut u64, final_out: *mut u64,
+    ) -> c_int;
+    pub fn p2hot_fri_pow_many(
+        ctx: *mut P2hotCtx, M: usize, challengers: *const *mut P2hotChallenger, pow_bits: c_uint, witnesses_out: *mut u64,
+    ) -> c_int;
     // ---- prover session (host pointers)
     pub fn p2hot_commit(
         ctx: *mut P2hotCtx, cols: *const *const u64, W: usize, log_n: c_uint, rate_bits: c_uint, cap_height: c_uint, is_values: c_int,

@@ -150,6 +150,8 @@ SIGNATURES = {
     "p2hot_merkle_paths_dev": (i, [vp, vp, u, u, vp, sz, vp]),
     "p2hot_partial_products_dev": (i, [vp, vp, sz, vp, sz, vp, u, u, u, vp, vp, u, vp, sz]),
     "p2hot_fri_pow": (i, [vp, vp, u, C.POINTER(u64)]),
+    "p2hot_fri_commit_many_dev": (i, [vp, sz, vp, u, u, u, C.POINTER(u), u, u, sz, C.POINTER(vp), vp, vp, i, vp, vp, vp]),
+    "p2hot_fri_pow_many": (i, [vp, sz, C.POINTER(vp), u, C.POINTER(u64)]),
     "p2hot_commit": (i, [vp, C.POINTER(vp), sz, u, u, u, i, u, vp, vp, vp, vp, C.POINTER(vp)]),
     "p2hot_commit_salted": (i, [vp, C.POINTER(vp), sz, u, u, u, i, u, C.POINTER(vp), sz, vp, vp, vp, vp, C.POINTER(vp)]),
     "p2hot_commit_cols": (i, [vp, vp, u, u, i, u, vp, vp, vp, vp, C.POINTER(vp)]),

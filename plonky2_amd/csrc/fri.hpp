@@ -708,4 +708,396 @@ __global__ void __launch_bounds__(256) batch_paths_kernel(const u64 *digests, Ba
     for (int w = 0; w < 4; ++w) out[4 * e + w] = src[w];
 }
 
+// ---- M proofs of one shape per launch (p2hot_fri_commit_many_dev, p2hot_fri_pow_many) ----
+// The commit phase and the grind of a recursion-size proof are chains of launches that leave the chip idle; M proofs share
+// nothing, so each kernel below is its single-proof kernel with the proof on a grid axis.  Coefficient planes are [2][M][len]
+// (plane p of proof y at (p * M + y) * len, M = gridDim.y): the 2M columns of one LDE.  The single-proof kernels above are
+// untouched; these repeat their arithmetic statement by statement, so every word equals the single call's.
+
+// challenger_kernel for M transcripts: workgroup blockIdx.x advances chs[blockIdx.x], observes obs[blockIdx.x * obs_stride + i]
+// (obs_stride = 0: every transcript observes the same words -- the zero caps and the zero padding of prover.rs:122-147) and
+// writes its challenges to out[blockIdx.x * out_stride + i].  A Poseidon digest is its 4 words (challenger.rs:69-80), so a cap of
+// c digests in their slots is observed as n_obs = 4 c.  n_in / n_out are per transcript: transcripts whose buffers are filled
+// differently take different numbers of duplexes, which is per-workgroup control flow.  One transcript per wave, as above.
+__global__ void __launch_bounds__(64) challenger_many_kernel(Challenger *const *__restrict__ chs, const u64 *obs, size_t obs_stride,
+                                                            size_t n_obs, u64 *out, size_t out_stride, size_t n_get) {
+    __shared__ u64 inbuf[8];
+    __shared__ u64 outbuf[8];
+    Challenger *ch = chs[blockIdx.x];
+    obs += (size_t)blockIdx.x * obs_stride;
+    out += (size_t)blockIdx.x * out_stride;
+    const unsigned lane = threadIdx.x, r = lane & 15;
+    const bool owner = lane < 12;
+    u32 n_in = ch->n_in, n_out = ch->n_out;
+    u64 w = owner ? ch->state[lane] : 0;
+    if (lane < 8) {
+        inbuf[lane] = ch->in[lane];
+        outbuf[lane] = ch->out[lane];
+    }
+    __syncthreads();
+    const poseidon16::RowConsts k = poseidon16::row_consts(r);
+    auto duplex = [&]() {  // challenger.rs:129-144
+        if (owner && lane < n_in) w = inbuf[lane];
+        poseidon16::permute_row(w, r, k);
+        w = gl::canon(w);
+        if (lane < 8) outbuf[lane] = w;
+        n_in = 0;
+        n_out = 8;
+        __syncthreads();
+    };
+    for (size_t i = 0; i < n_obs; ++i) {
+        n_out = 0;
+        if (lane == 0) inbuf[n_in] = gl::canon(obs[i]);
+        ++n_in;
+        __syncthreads();
+        if (n_in == 8) duplex();
+    }
+    for (size_t i = 0; i < n_get; ++i) {
+        if (n_in != 0 || n_out == 0) duplex();
+        --n_out;
+        if (lane == 0) out[i] = outbuf[n_out];
+    }
+    __syncthreads();
+    if (owner) ch->state[lane] = w;
+    if (lane < 8) {
+        ch->in[lane] = inbuf[lane];
+        ch->out[lane] = outbuf[lane];
+    }
+    if (lane == 0) {
+        ch->n_in = n_in;
+        ch->n_out = n_out;
+    }
+}
+
+// fold_kernel for M proofs, grid (blocks, M): c [2][M][m_out << arity_bits] -> o [2][M][m_out], beta of proof y at beta[2 y]
+__global__ void __launch_bounds__(256) fold_many_kernel(const u64 *c, unsigned arity_bits, const u64 *beta, size_t m_out, u64 *o) {
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m_out) return;
+    const size_t y = blockIdx.y, M = gridDim.y, len = m_out << arity_bits;
+    const u64 *c0 = c + y * len, *c1 = c + (M + y) * len;
+    gl::ext2 b{beta[2 * y], beta[2 * y + 1]};
+    gl::ext2 acc{0, 0};
+    const size_t base = j << arity_bits;
+    for (unsigned i = 1u << arity_bits; i-- > 0;) {
+        acc = gl::ext_mul(acc, b);
+        acc.a0 = gl::add(acc.a0, c0[base + i]);
+        acc.a1 = gl::add(acc.a1, c1[base + i]);
+    }
+    o[y * m_out + j] = gl::canon(acc.a0);
+    o[(M + y) * m_out + j] = gl::canon(acc.a1);
+}
+
+// interleave_kernel for M proofs, grid (blocks, M): planes p [2][M][count] -> proof y's [count][2] at out + y * out_stride
+// (the round leaves of proof y inside its own leaf block; the final polynomials back to back)
+__global__ void __launch_bounds__(256) interleave_many_kernel(const u64 *p, size_t count, u64 *out, size_t out_stride) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const size_t y = blockIdx.y, M = gridDim.y;
+    u64 *o = out + y * out_stride;
+    o[2 * i] = gl::canon(p[y * count + i]);
+    o[2 * i + 1] = gl::canon(p[(M + y) * count + i]);
+}
+
+// ---- the prelude of prove_openings for M proofs (final_poly_many_core): grid row y = proof, planes [2][M][len] ----
+// What the single-proof launches take by value comes from device tables here: alpha of proof y from its two device words, the
+// points from zt [M][n_batches][6] = z | z^L | z^G per batch (L = chunk length, G = L << group_log; canonical words, computed on
+// the host as the single path computes its arguments).  `zt` points at the batch's entry of proof 0, zt_stride words further on
+// is proof 1's; `which` picks z (0), z^L (1) or z^G (2).
+__device__ __forceinline__ gl::ext2 many_point(const u64 *zt, size_t zt_stride, unsigned which) {
+    const u64 *e = zt + (size_t)blockIdx.y * zt_stride + 2 * which;
+    return gl::ext2{e[0], e[1]};
+}
+
+// alpha_powers_kernel: out [M][count][2], alpha of proof y at alpha[y * alpha_stride]
+__global__ void __launch_bounds__(256) alpha_powers_many_kernel(const u64 *alpha, size_t alpha_stride, size_t count, u64 *out) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    alpha += (size_t)blockIdx.y * alpha_stride;
+    out += 2 * (size_t)blockIdx.y * count;
+    gl::ext2 w{1, 0}, b{gl::canon(alpha[0]), gl::canon(alpha[1])};
+    for (size_t e = j; e; e >>= 1) {
+        if (e & 1) w = gl::ext_mul(w, b);
+        b = gl::ext_mul(b, b);
+    }
+    out[2 * j] = gl::canon(w.a0);
+    out[2 * j + 1] = gl::canon(w.a1);
+}
+
+// reduce_polys_base_kernel: proof y's pointers at polys[y * table_stride ..], its alpha powers at apow[y * apow_stride ..]
+__global__ void __launch_bounds__(256) reduce_polys_base_many_kernel(const u64 *const *polys, size_t table_stride, size_t n_polys,
+                                                                    const u64 *apow, size_t apow_stride, size_t n, u64 *o) {
+    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const size_t y = blockIdx.y, M = gridDim.y;
+    polys += y * table_stride;
+    apow += y * apow_stride;
+    u64 a0 = 0, a1 = 0;
+    for (size_t j = 0; j < n_polys; ++j) {
+        u64 p = polys[j][t];
+        a0 = gl::add(a0, gl::mul(apow[2 * j], p));
+        a1 = gl::add(a1, gl::mul(apow[2 * j + 1], p));
+    }
+    o[y * n + t] = a0;
+    o[(M + y) * n + t] = a1;
+}
+
+// reduce_polys_base_small_kernel, the same way
+__global__ void __launch_bounds__(1024) reduce_polys_base_small_many_kernel(const u64 *const *polys, size_t table_stride, size_t n_polys,
+                                                                           const u64 *apow, size_t apow_stride, size_t n, u64 *o) {
+    __shared__ u64 s0[16][64], s1[16][64];
+    const unsigned lane = threadIdx.x & 63u, g = threadIdx.x >> 6;
+    const size_t t = (size_t)blockIdx.x * 64 + lane;
+    const size_t y = blockIdx.y, M = gridDim.y;
+    polys += y * table_stride;
+    apow += y * apow_stride;
+    u64 a0 = 0, a1 = 0;
+    if (t < n)
+        for (size_t j = g; j < n_polys; j += 16) {
+            u64 p = polys[j][t];
+            a0 = gl::add(a0, gl::mul(apow[2 * j], p));
+            a1 = gl::add(a1, gl::mul(apow[2 * j + 1], p));
+        }
+    s0[g][lane] = a0;
+    s1[g][lane] = a1;
+    __syncthreads();
+    for (unsigned d = 8; d; d >>= 1) {
+        if (g < d) {
+            s0[g][lane] = gl::add(s0[g][lane], s0[g + d][lane]);
+            s1[g][lane] = gl::add(s1[g][lane], s1[g + d][lane]);
+        }
+        __syncthreads();
+    }
+    if (g == 0 && t < n) {
+        o[y * n + t] = s0[0][lane];
+        o[(M + y) * n + t] = s1[0][lane];
+    }
+}
+
+// horner_chunk_totals_kernel: c [2][M][n_chunks << chunk_log] -> p [2][M][n_chunks]
+__global__ void __launch_bounds__(256) horner_chunk_totals_many_kernel(const u64 *c, unsigned chunk_log, size_t n_chunks, const u64 *zt,
+                                                                      size_t zt_stride, unsigned which, u64 *p) {
+    size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_chunks) return;
+    const size_t y = blockIdx.y, M = gridDim.y, len = n_chunks << chunk_log;
+    const u64 *c0 = c + y * len, *c1 = c + (M + y) * len;
+    const gl::ext2 z = many_point(zt, zt_stride, which);
+    gl::ext2 acc{0, 0};
+    const size_t base = m << chunk_log;
+    for (size_t i = (size_t)1 << chunk_log; i-- > 0;) {
+        acc = gl::ext_mul(acc, z);
+        acc.a0 = gl::add(acc.a0, c0[base + i]);
+        acc.a1 = gl::add(acc.a1, c1[base + i]);
+    }
+    p[y * n_chunks + m] = acc.a0;
+    p[(M + y) * n_chunks + m] = acc.a1;
+}
+
+// horner_carries_kernel, grid (1, M): one 1024-thread block per proof; p, t [2][M][n_chunks]
+__global__ void __launch_bounds__(1024) horner_carries_many_kernel(const u64 *p, size_t n_chunks, size_t per, const u64 *zt, size_t zt_stride,
+                                                                  unsigned which, u64 *t) {
+    __shared__ u64 s0[1024], s1[1024];
+    const size_t y = blockIdx.y, M = gridDim.y;
+    const u64 *p0 = p + y * n_chunks, *p1 = p + (M + y) * n_chunks;
+    u64 *t0 = t + y * n_chunks, *t1 = t + (M + y) * n_chunks;
+    const gl::ext2 zL = many_point(zt, zt_stride, which);
+    const unsigned tid = threadIdx.x;
+    const size_t lo = (size_t)tid * per, hi = lo + per < n_chunks ? lo + per : n_chunks;
+    gl::ext2 loc{0, 0};
+    for (size_t m = hi; m-- > lo;) {
+        loc = gl::ext_mul(loc, zL);
+        loc.a0 = gl::add(loc.a0, p0[m]);
+        loc.a1 = gl::add(loc.a1, p1[m]);
+    }
+    gl::ext2 zP{1, 0};  // zL^per
+    for (size_t g = 0; g < per; ++g) zP = gl::ext_mul(zP, zL);
+    s0[tid] = lo < n_chunks ? loc.a0 : 0;
+    s1[tid] = lo < n_chunks ? loc.a1 : 0;
+    __syncthreads();
+    gl::ext2 f = zP;
+    for (unsigned d = 1; d < 1024; d <<= 1) {
+        gl::ext2 add{0, 0};
+        if (tid + d < 1024) add = gl::ext_mul(gl::ext2{s0[tid + d], s1[tid + d]}, f);
+        __syncthreads();
+        s0[tid] = gl::add(s0[tid], add.a0);
+        s1[tid] = gl::add(s1[tid], add.a1);
+        __syncthreads();
+        f = gl::ext_mul(f, f);
+    }
+    gl::ext2 carry{0, 0};
+    if (tid + 1 < 1024) carry = gl::ext2{s0[tid + 1], s1[tid + 1]};
+    for (size_t m = hi; m-- > lo;) {
+        t0[m] = carry.a0;
+        t1[m] = carry.a1;
+        carry = gl::ext_mul(carry, zL);
+        carry.a0 = gl::add(carry.a0, p0[m]);
+        carry.a1 = gl::add(carry.a1, p1[m]);
+    }
+}
+
+// horner_group_walk_kernel: p, t [2][M][n_groups << group_log], T [2][M][n_groups]
+__global__ void __launch_bounds__(256) horner_group_walk_many_kernel(const u64 *p, unsigned group_log, size_t n_groups, const u64 *zt,
+                                                                    size_t zt_stride, const u64 *T, u64 *t) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    const size_t y = blockIdx.y, M = gridDim.y, n_chunks = n_groups << group_log;
+    const u64 *p0 = p + y * n_chunks, *p1 = p + (M + y) * n_chunks;
+    u64 *t0 = t + y * n_chunks, *t1 = t + (M + y) * n_chunks;
+    const gl::ext2 zL = many_point(zt, zt_stride, 1);
+    gl::ext2 carry{T[y * n_groups + g], T[(M + y) * n_groups + g]};
+    const size_t base = g << group_log;
+    for (size_t i = (size_t)1 << group_log; i-- > 0;) {
+        const size_t m = base + i;
+        t0[m] = carry.a0;
+        t1[m] = carry.a1;
+        carry = gl::ext_mul(carry, zL);
+        carry.a0 = gl::add(carry.a0, p0[m]);
+        carry.a1 = gl::add(carry.a1, p1[m]);
+    }
+}
+
+// horner_emit_kernel: c, a [2][M][n], t [2][M][n_chunks]; the shift of proof y at shift[y * shift_stride]
+__global__ void __launch_bounds__(256) horner_emit_many_kernel(const u64 *c, unsigned chunk_log, size_t n_chunks, const u64 *zt, size_t zt_stride,
+                                                              const u64 *t, const u64 *shift_ptr, size_t shift_stride, int accumulate, u64 *a) {
+    size_t m = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_chunks) return;
+    const size_t y = blockIdx.y, M = gridDim.y, n = n_chunks << chunk_log;
+    const u64 *c0 = c + y * n, *c1 = c + (M + y) * n;
+    u64 *a0 = a + y * n, *a1 = a + (M + y) * n;
+    const gl::ext2 z = many_point(zt, zt_stride, 0);
+    shift_ptr += y * shift_stride;
+    const gl::ext2 shift{shift_ptr[0], shift_ptr[1]};
+    gl::ext2 acc{t[y * n_chunks + m], t[(M + y) * n_chunks + m]};
+    const size_t base = m << chunk_log;
+    for (size_t i = (size_t)1 << chunk_log; i-- > 0;) {
+        const size_t k = base + i;
+        if (k == n - 1) {  // the padding coefficient of the quotient ("pad back to power of two", oracle.rs:209)
+            gl::ext2 prev = accumulate ? gl::ext_mul(gl::ext2{a0[k], a1[k]}, shift) : gl::ext2{0, 0};
+            a0[k] = gl::canon(prev.a0);
+            a1[k] = gl::canon(prev.a1);
+        }
+        acc = gl::ext_mul(acc, z);
+        acc.a0 = gl::add(acc.a0, c0[k]);
+        acc.a1 = gl::add(acc.a1, c1[k]);
+        if (k >= 1) {  // quotient[k-1] = b_k
+            gl::ext2 prev = accumulate ? gl::ext_mul(gl::ext2{a0[k - 1], a1[k - 1]}, shift) : gl::ext2{0, 0};
+            a0[k - 1] = gl::canon(gl::add(prev.a0, acc.a0));
+            a1[k - 1] = gl::canon(gl::add(prev.a1, acc.a1));
+        }
+    }
+}
+
+// ---- the query rounds of M proofs (prove_openings_many_core): grid row y = proof ----
+// The trees a launch opens, one entry per proof: a matrix (column-major LDE of an initial oracle, or the row-major leaves of a
+// round tree), its digest array, the words between columns (column-major only).  A read-only device table, indexed by blockIdx.y.
+struct ManyTree {
+    const u64 *mat, *dig;
+    size_t stride;
+};
+// Every kernel below writes QUERY-MAJOR into proof y's staging block (out + y * out_stride): query q's record of `rec` words starts at
+// q * rec, and this launch fills the words [off, off + w) of it -- the layout of the proof buffers of p2hot.h, so one copy brings a
+// proof's buffer back as it is.
+
+// the transcripts before the tail, and back (the grind-miss path): dir 0 saves chs[y] to save[y], 1 restores
+__global__ void __launch_bounds__(64) challenger_copy_many_kernel(Challenger *const *__restrict__ chs, Challenger *save, int dir) {
+    static_assert(sizeof(Challenger) % 8 == 0, "whole words");
+    u64 *a = reinterpret_cast<u64 *>(chs[blockIdx.x]), *b = reinterpret_cast<u64 *>(save + blockIdx.x);
+    if (threadIdx.x < sizeof(Challenger) / 8) {
+        if (dir)
+            a[threadIdx.x] = b[threadIdx.x];
+        else
+            b[threadIdx.x] = a[threadIdx.x];
+    }
+}
+
+// query_indices_kernel: rand [M][n_queries] -> idx [M][1 + n_rounds][n_queries]
+__global__ void __launch_bounds__(256) query_indices_many_kernel(const u64 *rand, size_t n_queries, unsigned log_n_total, ArityBits ab,
+                                                                unsigned n_rounds, u64 *idx) {
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_queries) return;
+    rand += (size_t)blockIdx.y * n_queries;
+    idx += (size_t)blockIdx.y * (1 + (size_t)n_rounds) * n_queries;
+    u64 x = gl::canon(rand[q]) & ((((u64)1) << log_n_total) - 1);
+    idx[q] = x;
+    for (unsigned r = 0; r < n_rounds; ++r) {
+        x >>= ab.b[r];
+        idx[(1 + (size_t)r) * n_queries + q] = x;
+    }
+}
+
+// MerkleTree::get for the m queries of every proof: rows idx[y * idx_stride + q] of proof y's matrix, w words each.  col_major: an
+// initial oracle's LDE (p2hot_gather_rows_dev's rows), else a round tree's leaves (gather_rowmajor_kernel).  An index past n_rows
+// zeroes its words and raises *oob.
+__global__ void __launch_bounds__(256) gather_rows_many_kernel(const ManyTree *__restrict__ trees, int col_major, size_t w, size_t n_rows,
+                                                              const u64 *idx, size_t idx_stride, size_t m, u64 *out, size_t out_stride, size_t rec,
+                                                              size_t off, unsigned *oob) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m * w) return;
+    const size_t q = e / w, c = e % w;
+    const ManyTree tr = trees[blockIdx.y];
+    const u64 r = idx[(size_t)blockIdx.y * idx_stride + q];
+    u64 *o = out + (size_t)blockIdx.y * out_stride + q * rec + off + c;
+    if (r >= n_rows) {
+        *o = 0;
+        if (c == 0) atomicOr(oob, 1u);
+        return;
+    }
+    *o = gl::canon(col_major ? tr.mat[c * tr.stride + r] : tr.mat[r * w + c]);
+}
+
+// merkle_paths_kernel for the m queries of every proof, from proof y's digest array
+__global__ void __launch_bounds__(256) merkle_paths_many_kernel(const ManyTree *__restrict__ trees, unsigned log_leaves, unsigned cap_height,
+                                                               const u64 *idx, size_t idx_stride, size_t m, u64 *out, size_t out_stride, size_t rec,
+                                                               size_t off, unsigned *oob) {
+    const unsigned layers = log_leaves - cap_height;
+    size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (layers == 0 || e >= m * layers) return;
+    const size_t q = e / layers;
+    const unsigned i = (unsigned)(e % layers);
+    const u64 *digests = trees[blockIdx.y].dig;
+    const size_t leaf = idx[(size_t)blockIdx.y * idx_stride + q];
+    u64 *o = out + (size_t)blockIdx.y * out_stride + q * rec + off + 4 * (size_t)i;
+    if (leaf >> log_leaves) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) o[w] = 0;
+        if (i == 0) atomicOr(oob, 2u);
+        return;
+    }
+    const size_t tree_len = 2 * (((size_t)1 << layers) - 1);
+    const size_t pair = (leaf & (((size_t)1 << layers) - 1)) >> i;  // pair_index before this layer's shift
+    const size_t parity = pair & 1;
+    const size_t siblings_index = ((pair >> 1) << (i + 1)) + ((size_t)1 << i) - 1;
+    const u64 *src = digests + 4 * (tree_len * (leaf >> layers) + 2 * siblings_index + (1 - parity));
+#pragma unroll
+    for (int w = 0; w < 4; ++w) o[w] = src[w];
+}
+
+// pow_kernel for M transcripts, grid (blocks, M): the candidates [start, start + count) against transcript y, best[y] by the same
+// minimum.  A block of proof y retires at once when best[y] was set by an earlier launch; the launches (pow_search_dev's chunk
+// schedule) are shared by all proofs.
+__global__ void __launch_bounds__(256) pow_many_kernel(const Challenger *const *__restrict__ chs, unsigned pow_bits, u64 start, u64 count,
+                                                      unsigned long long *best) {
+    u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const Challenger *ch = chs[blockIdx.y];
+    best += blockIdx.y;
+    if (*best < (unsigned long long)start) return;
+#ifndef P2HOT_EMU
+    // the permutation below takes every scalar register (pow_kernel spills four of them into vector lanes): what is only needed
+    // after it -- where the minimum goes, the bound -- waits in vector registers instead
+    asm volatile("" : "+v"(best), "+v"(pow_bits));
+#endif
+    u64 s[12];
+    const u32 n_in = ch->n_in;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = ((u32)i < n_in && i < 8) ? ch->in[i < 8 ? i : 0] : ch->state[i];
+    const u64 cand = start + t;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        if ((u32)i == n_in) s[i] = cand;
+    poseidon::permute(s);
+    u64 resp = gl::canon(s[7]);
+    unsigned lz = resp ? (unsigned)__clzll((long long)resp) : 64u;
+    if (lz >= pow_bits) atomicMin(best, (unsigned long long)cand);
+}
+
 }  // namespace fri

@@ -1137,6 +1137,215 @@ static int helper_contexts(p2hot_ctx *ctx, size_t want) {
     return P2HOT_OK;
 }
 
+// ------------------------------------------------------------------ M opening proofs of one shape in one set of launches
+// "One shape": distinct Poseidon transcripts and Poseidon oracles (the caller has refused Keccak), the same number of batches, the same
+// (oracle_index, poly_index) lists in every batch -- the points are per proof -- and the same polynomial and salt widths per oracle
+// position.  Anything else (a list that names a polynomial which does not exist included) takes the side-by-side path, which reports it.
+static bool many_one_shape(size_t M, const p2hot_fri_batch_info *const *batches, const size_t *n_batches,
+                           const std::vector<std::vector<OracleView>> &views, p2hot_challenger *const *challengers) {
+    std::set<const p2hot_challenger *> seen;
+    for (size_t j = 0; j < M; ++j) {
+        if (!seen.insert(challengers[j]).second) return false;
+        if (n_batches[j] != n_batches[0] || (n_batches[j] && !batches[j])) return false;
+        for (size_t o = 0; o < views[j].size(); ++o)
+            if (views[j][o].W != views[0][o].W || views[j][o].S != views[0][o].S) return false;
+        for (size_t i = 0; i < n_batches[j]; ++i) {
+            const p2hot_fri_batch_info &a = batches[0][i], &b = batches[j][i];
+            if (b.n_polys != a.n_polys || (b.n_polys && (!b.oracle_index || !b.poly_index))) return false;
+            for (size_t k = 0; k < b.n_polys; ++k) {
+                if (b.oracle_index[k] != a.oracle_index[k] || b.poly_index[k] != a.poly_index[k]) return false;
+                if (j == 0 && (b.oracle_index[k] >= views[0].size() || b.poly_index[k] >= views[0][b.oracle_index[k]].W)) return false;
+            }
+        }
+    }
+    return true;
+}
+
+// PolynomialBatch::prove_openings + fri_proof (fri/oracle.rs:176-237, fri/prover.rs:24-82) for M proofs of one shape: every launch
+// of prove_openings_core once per GROUP of proofs (fri_many_group), the proof on a grid axis, on the caller's context and stream.
+// Per group: alpha_j, the final polynomials as planes [2][g][n], the commit phase (the round trees of a round are one forest), the
+// grind, the witness and the query indices, then the rows and paths of the g oracles of each oracle position and of the g round
+// trees of each round, written query-major into one staging block -- a proof's four query buffers as p2hot.h lays them out -- that
+// one copy brings to a pinned block.  The groups reuse the device blocks in stream order; ONE synchronisation ends the call and the
+// host scatters the staging into the callers' buffers.  Everything is validated before the first enqueue.
+// A proof whose device-searched grind range held no witness (probability e^-32) gets its transcript back as it was before the call
+// and is proved again alone, by the single-proof path with its host-checked grind; the other proofs of the call stand.
+static int prove_openings_many_core(p2hot_ctx *ctx, size_t M, const p2hot_fri_batch_info *const *batches, size_t n_batches,
+                                    const std::vector<std::vector<OracleView>> &views, unsigned log_n, p2hot_challenger *const *challengers,
+                                    const p2hot_fri_params *fp, p2hot_fri_proof *proofs) {
+    const char *what = "prove_openings_many";
+    FriRounds rounds;
+    P2_TRY(fri_check_params(ctx, fp, log_n, &rounds));
+    const unsigned rate_bits = fp->rate_bits, cap_height = fp->cap_height, log_N = log_n + rate_bits, R = fp->n_reduction_rounds;
+    const size_t Q = fp->num_query_rounds, n = (size_t)1 << log_n, N = n << rate_bits, n_oracles = views[0].size();
+    if (R > 32) P2_FAIL(ctx, P2HOT_EINVAL, "%s: more than 32 reduction rounds", what);
+    if (fp->proof_of_work_bits > 64) P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof_of_work_bits > 64", what);
+    std::vector<size_t> leaf_widths;
+    size_t w_sum = 0;
+    for (auto &v : views[0]) {
+        leaf_widths.push_back(v.leaf_width());
+        w_sum += v.leaf_width();
+    }
+    p2hot_fri_proof_layout lay;
+    if (fri_proof_layout(leaf_widths.data(), n_oracles, log_n, fp, &lay) != P2HOT_OK) P2_FAIL(ctx, P2HOT_EINVAL, "%s: inconsistent parameters", what);
+    for (size_t j = 0; j < M; ++j) {
+        const p2hot_fri_proof &pr = proofs[j];
+        if ((lay.caps_words && !pr.commit_phase_merkle_caps) || !pr.final_poly ||
+            (Q && ((lay.initial_leaves_words && !pr.initial_leaves) || (lay.initial_paths_words && !pr.initial_paths) ||
+                   (lay.step_evals_words && !pr.step_evals) || (lay.step_paths_words && !pr.step_paths))))
+            P2_FAIL(ctx, P2HOT_EINVAL, "%s: proof %zu: a proof buffer is null (size them with p2hot_fri_proof_sizes)", what, j);
+    }
+    // the polynomial table of the shared instance (FriInstanceInfo.batches, fri/structure.rs) and every proof's points
+    std::vector<size_t> offsets(1, 0);
+    for (size_t i = 0; i < n_batches; ++i) offsets.push_back(offsets.back() + batches[0][i].n_polys);
+    const size_t total = offsets.back(), G = fri_many_group(M, log_N), idx_words = (1 + (size_t)R) * Q;
+    const unsigned layers0 = log_N - cap_height;
+    const size_t caps_words = lay.caps_words, final_words = lay.final_poly_words;
+    // a proof's staging record: its four query buffers, query-major
+    const size_t o_leaves = 0, o_paths = o_leaves + lay.initial_leaves_words, o_evals = o_paths + lay.initial_paths_words,
+                 o_steps = o_evals + lay.step_evals_words, rec = Q ? o_steps + lay.step_paths_words : 0;
+    PoolBuf d_small(ctx), d_planes(ctx), d_leaves(ctx), d_dig(ctx), d_q(ctx), d_save(ctx), fp_scratch(ctx), commit_scratch(ctx);
+    P2_TRY(pool_alloc(ctx, 2 * G * n * 8, &d_planes.p));
+    P2_TRY(pool_alloc(ctx, (rounds.leaf_words ? G * rounds.leaf_words : 1) * 8, &d_leaves.p));
+    P2_TRY(pool_alloc(ctx, (rounds.dig_words ? G * rounds.dig_words : 1) * 8, &d_dig.p));
+    P2_TRY(pool_alloc(ctx, M * sizeof(fri::Challenger), &d_save.p));
+    // alpha [G][2] | witness [G] | response [G] | rand [G][Q] | idx [G][1 + R][Q] | staging [G][rec]
+    P2_TRY(pool_alloc(ctx, G * (4 + Q + idx_words + rec) * 8, &d_q.p));
+    u64 *q_alpha = d_q.u(), *q_best = q_alpha + 2 * G, *q_resp = q_best + G, *q_rand = q_resp + G, *q_idx = q_rand + G * Q, *q_stage = q_idx + G * idx_words;
+    // one small upload: transcripts [M] | polynomial pointers [M][total] | initial trees [n_oracles][M] | round trees [R][G]
+    static_assert(sizeof(fri::ManyTree) == 24 && sizeof(fri::Challenger *) == 8, "table words");
+    const size_t s_tab = M, s_init = s_tab + M * total, s_round = s_init + 3 * n_oracles * M, small_words = s_round + 3 * (size_t)R * G;
+    std::vector<u64> small(small_words), pts(2 * M * n_batches + 1), zt(6 * M * n_batches + 1);
+    P2_TRY(pool_alloc(ctx, small_words * 8, &d_small.p));
+    for (size_t j = 0; j < M; ++j) {
+        small[j] = (u64)(uintptr_t)challengers[j]->d;
+        u64 *tab = small.data() + s_tab + j * total;
+        for (size_t i = 0, k = 0; i < n_batches; ++i) {
+            const p2hot_fri_batch_info &bi = batches[j][i];
+            for (size_t e = 0; e < bi.n_polys; ++e, ++k) {
+                const OracleView &v = views[j][bi.oracle_index[e]];
+                tab[k] = (u64)(uintptr_t)(v.d_coef + bi.poly_index[e] * v.col_coef(log_n));
+            }
+            pts[2 * (j * n_batches + i)] = bi.point[0];
+            pts[2 * (j * n_batches + i) + 1] = bi.point[1];
+        }
+        for (size_t o = 0; o < n_oracles; ++o) {
+            const OracleView &v = views[j][o];
+            u64 *t = small.data() + s_init + 3 * (o * M + j);
+            t[0] = (u64)(uintptr_t)v.d_lde, t[1] = (u64)(uintptr_t)v.d_dig, t[2] = v.col_lde();
+        }
+    }
+    for (unsigned r = 0; r < R; ++r)
+        for (size_t y = 0; y < G; ++y) {  // proof y of a group: its slice of the group's round trees
+            u64 *t = small.data() + s_round + 3 * (r * G + y);
+            t[0] = (u64)(uintptr_t)(d_leaves.u() + y * rounds.leaf_words + rounds.round[r].leaf_off);
+            t[1] = (u64)(uintptr_t)(d_dig.u() + y * rounds.dig_words + rounds.round[r].dig_off);
+            t[2] = 0;
+        }
+    fri::Challenger *const *d_chs = reinterpret_cast<fri::Challenger *const *>(d_small.u());
+    const u64 *const *d_tables = reinterpret_cast<const u64 *const *>(d_small.u() + s_tab);
+    const fri::ManyTree *d_init = reinterpret_cast<const fri::ManyTree *>(d_small.u() + s_init);
+    const fri::ManyTree *d_round = reinterpret_cast<const fri::ManyTree *>(d_small.u() + s_round);
+    fri::ArityBits ab{};
+    for (unsigned r = 0; r < R; ++r) ab.b[r] = (unsigned char)rounds.round[r].arity_bits;
+    // host landing blocks: the staging records and the query indices (pinned, one copy each per group), caps, final polynomials, witnesses
+    struct Pinned {
+        p2hot_ctx *ctx;
+        void *p = nullptr;
+        ~Pinned() { p2hot_host_free(ctx, p); }
+    } h_block{ctx};
+    P2_TRY(p2hot_host_alloc(ctx, (M * (rec + idx_words) + 1) * 8, &h_block.p));
+    u64 *h_stage = (u64 *)h_block.p, *h_idx = h_stage + M * rec;
+    std::vector<u64> h_caps(M * caps_words + 1), h_final(M * final_words + 1);
+    std::vector<unsigned long long> best(M, ~0ull);
+    auto group = [&](size_t j0, size_t g) -> int {
+        const unsigned gy = (unsigned)g;
+        fri::Challenger *const *chs = d_chs + j0;
+        // oracle.rs:186: alpha_j = challenger_j.get_extension_challenge()
+        P2_TRY(challenger_many_dev(ctx, chs, g, nullptr, 0, 0, q_alpha, 2, 2));
+        // oracle.rs:190-213: the final polynomials, planes [2][g][n]
+        P2_TRY(final_poly_many_core(ctx, g, d_tables + j0 * total, total, offsets.data(), n_batches, pts.data() + 2 * j0 * n_batches, q_alpha, 2, log_n,
+                                    d_planes.u(), fp_scratch, zt.data() + 6 * j0 * n_batches));
+        // oracle.rs:215-220 + fri/prover.rs:40-51: the commit phase; the round trees stay on the device, proof-major
+        P2_TRY(fri_commit_many_core(ctx, g, d_planes.u(), log_n, rate_bits, cap_height, fp->reduction_arity_bits, R, fp->max_num_query_steps,
+                                    fp->final_poly_coeff_len, chs, rounds.leaf_words ? d_leaves.u() : nullptr, rounds.dig_words ? d_dig.u() : nullptr,
+                                    true, caps_words ? h_caps.data() + j0 * caps_words : nullptr, nullptr, h_final.data() + j0 * final_words,
+                                    commit_scratch));
+        // fri/prover.rs:53-58, :197-198: the grind, then observe the witness and draw the response
+        u64 pow_next = 0;
+        P2_TRY(pow_search_many_dev(ctx, chs, g, fp->proof_of_work_bits, (unsigned long long *)q_best, &pow_next));
+        P2_TRY(challenger_many_dev(ctx, chs, g, q_best, 1, 1, q_resp, 1, 1));
+        P2_TRY(d2h(ctx, best.data() + j0, q_best, g * 8));
+        if (Q == 0) return P2HOT_OK;
+        // fri/prover.rs:215-220, :243-253: the query indices
+        P2_TRY(challenger_many_dev(ctx, chs, g, nullptr, 0, 0, q_rand, Q, Q));
+        P2HOT_LAUNCH(fri::query_indices_many_kernel, dim3(cdiv(Q, 256), gy), dim3(256), 0, ctx->stream, (const u64 *)q_rand, Q, log_N, ab, R, q_idx);
+        P2_LAUNCH_CHECK(ctx);
+        // prover.rs:238-241: per oracle position (tree.get(x), tree.prove(x)) of the g oracles, all queries per launch
+        size_t w_off = 0;
+        for (size_t o = 0; o < n_oracles; ++o) {
+            const fri::ManyTree *tr = d_init + o * M + j0;
+            const size_t Wb = leaf_widths[o];
+            if (Wb)
+                P2HOT_LAUNCH(fri::gather_rows_many_kernel, dim3(cdiv(Q * Wb, 256), gy), dim3(256), 0, ctx->stream, tr, 1, Wb, N, (const u64 *)q_idx,
+                             idx_words, Q, q_stage + o_leaves, rec, w_sum, w_off, ctx->d_oob);
+            if (layers0)
+                P2HOT_LAUNCH(fri::merkle_paths_many_kernel, dim3(cdiv(Q * layers0, 256), gy), dim3(256), 0, ctx->stream, tr, log_N, cap_height,
+                             (const u64 *)q_idx, idx_words, Q, q_stage + o_paths, rec, n_oracles * 4 * layers0, o * 4 * layers0, ctx->d_oob);
+            P2_LAUNCH_CHECK(ctx);
+            w_off += Wb;
+        }
+        // prover.rs:242-253: per round (evals, tree.prove(x >> arity_bits)) of the g round trees
+        for (unsigned r = 0; r < R; ++r) {
+            const FriRound &f = rounds.round[r];
+            const u64 *idx_r = q_idx + (1 + (size_t)r) * Q;
+            P2HOT_LAUNCH(fri::gather_rows_many_kernel, dim3(cdiv(Q * f.ev_w, 256), gy), dim3(256), 0, ctx->stream, d_round + r * G, 0, f.ev_w,
+                         f.rows >> f.arity_bits, idx_r, idx_words, Q, q_stage + o_evals, rec, rounds.ev_words, f.ev_off, ctx->d_oob);
+            if (f.pa_w)
+                P2HOT_LAUNCH(fri::merkle_paths_many_kernel, dim3(cdiv(Q * (f.pa_w / 4), 256), gy), dim3(256), 0, ctx->stream, d_round + r * G, f.log_leaves,
+                             cap_height, idx_r, idx_words, Q, q_stage + o_steps, rec, rounds.pa_words, f.pa_off, ctx->d_oob);
+            P2_LAUNCH_CHECK(ctx);
+        }
+        if (rec) P2_HIP(ctx, hipMemcpyAsync(h_stage + j0 * rec, q_stage, g * rec * 8, hipMemcpyDeviceToHost, ctx->stream));
+        P2_HIP(ctx, hipMemcpyAsync(h_idx + j0 * idx_words, q_idx, g * idx_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return P2HOT_OK;
+    };
+    auto body = [&]() -> int {
+        P2_HIP(ctx, hipMemcpyAsync(d_small.p, small.data(), small_words * 8, hipMemcpyHostToDevice, ctx->stream));
+        // the transcripts as they arrive, for a proof that has to be proved again alone (see above)
+        P2HOT_LAUNCH(fri::challenger_copy_many_kernel, dim3((unsigned)M), dim3(64), 0, ctx->stream, d_chs, (fri::Challenger *)d_save.p, 0);
+        P2_LAUNCH_CHECK(ctx);
+        for (size_t j0 = 0; j0 < M; j0 += G) P2_TRY(group(j0, std::min(G, M - j0)));
+        return P2HOT_OK;
+    };
+    int rc = sync_checked(ctx, body(), what);
+    if (rc != P2HOT_OK) return rc;
+    for (size_t j = 0; j < M; ++j) {
+        p2hot_fri_proof &pr = proofs[j];
+        if (best[j] == ~0ull) {  // no witness in the device-searched range: this proof again, alone, from its transcript before the call
+            P2HOT_LAUNCH(fri::challenger_copy_many_kernel, dim3(1), dim3(64), 0, ctx->stream, d_chs + j, (fri::Challenger *)d_save.p + j, 1);
+            P2_LAUNCH_CHECK(ctx);
+            int one = prove_openings_views(ctx, batches[j], n_batches, views[j], log_n, challengers[j], fp, &pr, nullptr);
+            if (one != P2HOT_OK) {
+                const std::string inner = ctx->err;
+                P2_FAIL(ctx, one, "%s: proof %zu: %s", what, j, inner.c_str());
+            }
+            continue;
+        }
+        pr.pow_witness = best[j];
+        if (caps_words) std::copy(h_caps.begin() + j * caps_words, h_caps.begin() + (j + 1) * caps_words, pr.commit_phase_merkle_caps);
+        std::copy(h_final.begin() + j * final_words, h_final.begin() + (j + 1) * final_words, pr.final_poly);
+        if (Q == 0) continue;
+        const u64 *s = h_stage + j * rec;
+        if (pr.query_indices) std::copy(h_idx + j * idx_words, h_idx + j * idx_words + Q, pr.query_indices);
+        if (lay.initial_leaves_words) std::copy(s + o_leaves, s + o_paths, pr.initial_leaves);
+        if (lay.initial_paths_words) std::copy(s + o_paths, s + o_evals, pr.initial_paths);
+        if (lay.step_evals_words) std::copy(s + o_evals, s + o_steps, pr.step_evals);
+        if (lay.step_paths_words) std::copy(s + o_steps, s + rec, pr.step_paths);
+    }
+    return P2HOT_OK;
+}
+
 extern "C" int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_fri_batch_info *const *batches, const size_t *n_batches,
                                          const p2hot_batch *const *oracles, size_t n_oracles, p2hot_challenger *const *challengers,
                                          const p2hot_fri_params *fp, p2hot_fri_proof *proofs) {
@@ -1159,6 +1368,14 @@ extern "C" int p2hot_prove_openings_many(p2hot_ctx *ctx, size_t M, const p2hot_f
                 P2_FAIL(ctx, P2HOT_EINVAL, "prove_openings_many: oracle %zu of proof %zu was committed with another degree / rate / cap height", o, j);
             views[j].push_back(view_of(B));
         }
+    }
+    // The fused path: proofs of one shape share every launch (prove_openings_many_core below).  P2HOT_MANY_FUSED, read per call
+    // like P2HOT_MANY_HELPERS: 0 = always side by side; unset or 1 = fused where the proofs are eligible.
+    {
+        bool fused = true;
+        if (const char *e = getenv("P2HOT_MANY_FUSED")) fused = atoi(e) != 0;
+        if (fused && many_one_shape(M, batches, n_batches, views, challengers))
+            return prove_openings_many_core(ctx, M, batches, n_batches[0], views, oracles[0]->log_n, challengers, fp, proofs);
     }
     size_t k_max = 4;  // sibling contexts: 2 and 4 measured 1.8-1.9x a single stream, 8+ no better (P2HOT_MANY_HELPERS overrides; tools/pom_trace.py)
     if (const char *e = getenv("P2HOT_MANY_HELPERS")) k_max = std::max<size_t>(1, std::min<size_t>(64, (size_t)strtoull(e, nullptr, 10)));

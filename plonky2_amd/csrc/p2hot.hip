@@ -1918,6 +1918,76 @@ extern "C" int p2hot_fri_final_poly_dev(p2hot_ctx *ctx, const uint64_t *const *d
     return final_poly_core(ctx, d_poly_table, batch_offsets, n_batches, points, alpha, nullptr, log_n, d_final);
 }
 
+// final_poly_core for G proofs whose batches open the same polynomial positions: every launch of the single path once, over
+// all of them (fri.hpp, "the prelude of prove_openings for M proofs").  d_tables: device pointer tables, proof y's at
+// d_tables + y * table_stride in batch order; points: host [G][n_batches][2]; d_alpha: proof y's two device words at
+// d_alpha + y * alpha_stride; d_final: planes [2][G][n].  `blob` (6 * G * n_batches host words of the caller's: the host side of
+// the point table's upload) and `scratch` live until the caller has synchronised.  Nothing here waits for the GPU.
+static int final_poly_many_core(p2hot_ctx *ctx, size_t G, const uint64_t *const *d_tables, size_t table_stride, const size_t *batch_offsets,
+                                size_t n_batches, const uint64_t *points, const uint64_t *d_alpha, size_t alpha_stride, unsigned log_n,
+                                uint64_t *d_final, PoolBuf &scratch, u64 *blob) {
+    const size_t n = (size_t)1 << log_n;
+    // the chunking of final_poly_core
+    const unsigned chunk_log = log_n < 2 ? log_n : std::min(6u, std::max(2u, log_n > 10 ? log_n - 10 : 0u));
+    const size_t n_chunks = n >> chunk_log, per = (n_chunks + 1023) / 1024;
+    size_t max_j = 1;
+    for (size_t i = 0; i < n_batches; ++i) max_j = std::max(max_j, batch_offsets[i + 1] - batch_offsets[i]);
+    const unsigned group_log = 6;
+    const bool two_level = n_chunks > ctx->horner_two_level_min && n_chunks >= ((size_t)1 << group_log);
+    const size_t n_groups = two_level ? n_chunks >> group_log : 0, gper = (n_groups + 1023) / 1024;
+    const size_t apow_stride = 2 * (max_j + 1), zt_stride = 6 * n_batches;
+    // composition planes [2][G][n] | chunk totals, carries [2][G][n_chunks] each | group totals, carries [2][G][n_groups] each |
+    // alpha powers [G][max_j + 1][2] | points [G][n_batches][6]
+    const size_t words = G * (2 * n + 4 * n_chunks + 4 * n_groups + apow_stride + zt_stride);
+    if (!scratch.p) P2_TRY(pool_alloc(ctx, (words ? words : 1) * 8, &scratch.p));  // (by the first, largest group of a call)
+    u64 *c = scratch.u(), *p = c + 2 * G * n, *t = p + 2 * G * n_chunks, *g = t + 2 * G * n_chunks, *T = g + 2 * G * n_groups;
+    u64 *d_apow = T + 2 * G * n_groups, *d_zt = d_apow + G * apow_stride;
+    if (n_batches == 0) {
+        P2_HIP(ctx, hipMemsetAsync(d_final, 0, G * n * 16, ctx->stream));
+        return P2HOT_OK;
+    }
+    for (size_t e = 0; e < G * n_batches; ++e) {
+        const gl::ext2 z{gl::canon(points[2 * e]), gl::canon(points[2 * e + 1])};
+        const gl::ext2 zL = ext_pow(z, (u64)1 << chunk_log), zG = ext_pow(zL, (u64)1 << group_log);
+        u64 *o = blob + 6 * e;
+        o[0] = z.a0, o[1] = z.a1, o[2] = zL.a0, o[3] = zL.a1, o[4] = zG.a0, o[5] = zG.a1;
+    }
+    P2_HIP(ctx, hipMemcpyAsync(d_zt, blob, G * zt_stride * 8, hipMemcpyHostToDevice, ctx->stream));
+    const unsigned gy = (unsigned)G;
+    P2HOT_LAUNCH(fri::alpha_powers_many_kernel, dim3(cdiv(max_j + 1, 256), gy), dim3(256), 0, ctx->stream, d_alpha, alpha_stride, max_j + 1, d_apow);
+    P2_LAUNCH_CHECK(ctx);
+    for (size_t i = 0; i < n_batches; ++i) {
+        const size_t J = batch_offsets[i + 1] - batch_offsets[i];
+        const u64 *zt = d_zt + 6 * i;
+        {
+            ProfScope ps(ctx, "reduce_polys_base");
+            if (log_n <= 16)
+                P2HOT_LAUNCH(fri::reduce_polys_base_small_many_kernel, dim3(cdiv(n, 64), gy), dim3(1024), 0, ctx->stream, d_tables + batch_offsets[i],
+                             table_stride, J, (const u64 *)d_apow, apow_stride, n, c);
+            else
+                P2HOT_LAUNCH(fri::reduce_polys_base_many_kernel, dim3(cdiv(n, 256), gy), dim3(256), 0, ctx->stream, d_tables + batch_offsets[i],
+                             table_stride, J, (const u64 *)d_apow, apow_stride, n, c);
+            P2_LAUNCH_CHECK(ctx);
+        }
+        ProfScope ps(ctx, "divide_by_linear");
+        P2HOT_LAUNCH(fri::horner_chunk_totals_many_kernel, dim3(cdiv(n_chunks, 256), gy), dim3(256), 0, ctx->stream, (const u64 *)c, chunk_log,
+                     n_chunks, zt, zt_stride, 0u, p);
+        if (two_level) {
+            P2HOT_LAUNCH(fri::horner_chunk_totals_many_kernel, dim3(cdiv(n_groups, 256), gy), dim3(256), 0, ctx->stream, (const u64 *)p, group_log,
+                         n_groups, zt, zt_stride, 1u, g);
+            P2HOT_LAUNCH(fri::horner_carries_many_kernel, dim3(1, gy), dim3(1024), 0, ctx->stream, (const u64 *)g, n_groups, gper, zt, zt_stride, 2u, T);
+            P2HOT_LAUNCH(fri::horner_group_walk_many_kernel, dim3(cdiv(n_groups, 256), gy), dim3(256), 0, ctx->stream, (const u64 *)p, group_log,
+                         n_groups, zt, zt_stride, (const u64 *)T, t);
+        } else {
+            P2HOT_LAUNCH(fri::horner_carries_many_kernel, dim3(1, gy), dim3(1024), 0, ctx->stream, (const u64 *)p, n_chunks, per, zt, zt_stride, 1u, t);
+        }
+        P2HOT_LAUNCH(fri::horner_emit_many_kernel, dim3(cdiv(n_chunks, 256), gy), dim3(256), 0, ctx->stream, (const u64 *)c, chunk_log, n_chunks, zt,
+                     zt_stride, (const u64 *)t, (const u64 *)(d_apow + 2 * J), apow_stride, i > 0 ? 1 : 0, d_final);
+        P2_LAUNCH_CHECK(ctx);
+    }
+    return P2HOT_OK;
+}
+
 extern "C" int p2hot_eval_polys_dev(p2hot_ctx *ctx, const uint64_t *const *d_poly_table, size_t n_polys, unsigned log_n,
                                     const uint64_t *points, size_t n_points, uint64_t *d_out) {
     if (!ctx) return P2HOT_EINVAL;
@@ -2127,6 +2197,230 @@ extern "C" int p2hot_fri_pow(p2hot_ctx *ctx, p2hot_challenger *challenger, unsig
     *witness_out = best;
     u64 w = best, resp;
     return p2hot_challenger_step(challenger, &w, 1, &resp, 1);  // prover.rs:197-198
+}
+
+// ------------------------------------------------------------------ commit phase and grind of M proofs per set of launches
+// what the M-forms check of their transcripts, before anything is enqueued: M distinct Poseidon transcripts of this context
+static int challengers_many_check(p2hot_ctx *ctx, const char *what, size_t M, p2hot_challenger *const *challengers) {
+    if (!challengers) P2_FAIL(ctx, P2HOT_EINVAL, "%s: null challenger table", what);
+    std::set<const p2hot_challenger *> seen;
+    for (size_t j = 0; j < M; ++j) {
+        if (!challengers[j] || challengers[j]->ctx != ctx) P2_FAIL(ctx, P2HOT_EINVAL, "%s: challenger %zu is null or belongs to another context", what, j);
+        if (challengers[j]->hash_n)
+            P2_FAIL(ctx, P2HOT_EUNSUPPORTED, "%s: challenger %zu is a KeccakHash<%u> transcript (Keccak proofs: one at a time)", what, j,
+                    challengers[j]->hash_n);
+        if (!seen.insert(challengers[j]).second) P2_FAIL(ctx, P2HOT_EINVAL, "%s: challenger %zu is given twice", what, j);
+    }
+    return P2HOT_OK;
+}
+
+// Proofs per group of an M-form FRI call: the round scratch of a group (codewords [2][G][N], their forest's digests, the
+// coefficient planes) grows with G << log_N, bounded here by 2^22 extension elements (64 MiB of codewords, at most 128 MiB of
+// digests): 128 recursion-size proofs (N = 2^15) are one group.  2G LDE columns are grid rows of one launch, hence G <= 8192.
+// P2HOT_MANY_GROUP (read per call) lowers the bound (tests: two groups at M = 3).
+static size_t fri_many_group(size_t M, unsigned log_N) {
+    size_t g = log_N >= 22 ? 1 : std::min<size_t>(8192, (size_t)1 << (22 - log_N));
+    if (const char *e = getenv("P2HOT_MANY_GROUP")) {
+        const size_t v = (size_t)strtoull(e, nullptr, 10);
+        if (v >= 1 && v < g) g = v;
+    }
+    return std::min(g, M);
+}
+
+static int challenger_many_dev(p2hot_ctx *ctx, fri::Challenger *const *d_chs, size_t G, const u64 *d_obs, size_t obs_stride, size_t n_obs,
+                               u64 *d_out, size_t out_stride, size_t n_get) {
+    if (G == 0 || (n_obs == 0 && n_get == 0)) return P2HOT_OK;
+    P2HOT_LAUNCH(fri::challenger_many_kernel, dim3((unsigned)G), dim3(64), 0, ctx->stream, d_chs, d_obs, obs_stride, n_obs, d_out, out_stride,
+                 n_get);
+    P2_LAUNCH_CHECK(ctx);
+    return P2HOT_OK;
+}
+
+// fri_commit_core for M device plane sets [2][M][n] and M transcripts (d_chs: their device pointer table); the outputs are
+// proof-major (include/p2hot.h).  Enqueues only: the caller synchronises.  `scratch` is allocated by the first call that sees it
+// empty, for that call's M; a later call with the same block (the next group of p2hot_prove_openings_many) has no more proofs.
+static int fri_commit_many_core(p2hot_ctx *ctx, size_t M, const uint64_t *d_planar, unsigned log_n, unsigned rate_bits, unsigned cap_height,
+                                const unsigned *arity_bits, unsigned n_rounds, unsigned max_num_query_steps, size_t final_poly_coeff_len,
+                                fri::Challenger *const *d_chs, uint64_t *d_leaves_out, uint64_t *digests_out, bool digests_on_device,
+                                uint64_t *caps_out, uint64_t *betas_out, uint64_t *final_out, PoolBuf &scratch) {
+    const unsigned log_N = log_n + rate_bits;
+    const size_t n = (size_t)1 << log_n, N = n << rate_bits, cap_words = (size_t)4 << cap_height;
+    FriRounds rounds;
+    P2_TRY(fri_rounds(ctx, "fri_commit_many", log_n, rate_bits, cap_height, arity_bits, n_rounds, &rounds));
+    const size_t G = fri_many_group(M, log_N);
+    unsigned lg = 0;
+    while (((size_t)1 << lg) < G) ++lg;
+    size_t dig_max = 1;  // digest words of the widest round tree
+    for (const FriRound &f : rounds.round) dig_max = std::max(dig_max, 4 * p2hot_num_digests(f.log_leaves, cap_height));
+    const size_t n_final = (size_t)1 << (rounds.log_last >= rate_bits ? rounds.log_last - rate_bits : 0);
+    const size_t extra = final_poly_coeff_len > n_final ? 2 * (final_poly_coeff_len - n_final) : 0;  // zero words every transcript observes
+    const size_t zero_words = std::max(max_num_query_steps > n_rounds ? cap_words : 0, std::min(extra, 2 * N));
+    // one block, carved up: planes a, b [2][G][n] | values [2][G][N] | digests [G][dig_max] | caps [G][cap_words] | betas [G][2] |
+    // final polynomials [G][n][2] | zeros
+    const size_t words = 2 * (2 * G * n) + 2 * G * N + G * dig_max + G * cap_words + 2 * G + 2 * G * n + (zero_words ? zero_words : 1);
+    if (!scratch.p) P2_TRY(pool_alloc(ctx, words * 8, &scratch.p));
+    u64 *p = scratch.u();
+    u64 *planes_a = p, *planes_b = planes_a + 2 * G * n, *values = planes_b + 2 * G * n, *digests = values + 2 * G * N;
+    u64 *cap = digests + G * dig_max, *beta = cap + G * cap_words, *stage = beta + 2 * G, *zeros = stage + 2 * G * n;
+    if (zero_words) P2_HIP(ctx, hipMemsetAsync(zeros, 0, zero_words * 8, ctx->stream));
+    const size_t final_words = 2 * n_final;
+    for (size_t j0 = 0; j0 < M; j0 += G) {
+        const size_t g = std::min(G, M - j0);  // proofs of this group: planes [2][g][len]
+        unsigned lgg = 0;
+        while (((size_t)1 << lgg) < g) ++lgg;
+        fri::Challenger *const *chs = d_chs + j0;
+        u64 *cur = planes_a, *nxt = planes_b;
+        size_t cur_n = n;
+        for (unsigned c = 0; c < 2; ++c)  // the group's rows of both planes
+            P2_HIP(ctx, hipMemcpyAsync(cur + c * g * n, d_planar + (c * M + j0) * n, g * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        u64 shift = gl::COSET_SHIFT;
+        size_t m = N;
+        unsigned log_cur = log_n;
+        for (unsigned r = 0; r < n_rounds; ++r) {
+            const FriRound &f = rounds.round[r];
+            const unsigned ab = f.arity_bits;
+            // prover.rs:119 / oracle.rs:215-220: the g codewords are the 2g columns of one LDE, column = plane * g + proof
+            u64 *v0 = values, *v1 = v0 + g * m;
+            P2_TRY(p2hot_coset_lde_dev(ctx, cur, 2 * g, cur_n, log_cur, rate_bits, shift, 0, m, v0, m));
+            if (d_leaves_out) {
+                P2HOT_LAUNCH(fri::interleave_many_kernel, dim3(cdiv(m, 256), (unsigned)g), dim3(256), 0, ctx->stream, (const u64 *)v0, m,
+                             d_leaves_out + j0 * rounds.leaf_words + f.leaf_off, rounds.leaf_words);
+                P2_LAUNCH_CHECK(ctx);
+            }
+            // prover.rs:99-104: leaf L = j * 2^log_leaves + l of the forest reads proof j's chunk l: g << cap_height whole cap
+            // subtrees of a tree of 2^(log_leaves + ceil(log2 g)) leaves -- proof j's digests and cap entries are contiguous
+            P2_TRY(merkle_forest(ctx, merkle::FriPlanarReader{v0, v1, ab}, (size_t)2 << ab, f.log_leaves + lgg, cap_height + lgg, 0,
+                                 g << f.log_leaves, digests, cap, 0));
+            const size_t nd = p2hot_num_digests(f.log_leaves, cap_height);
+            if (digests_out && nd) {
+                u64 *dst = digests_out + j0 * rounds.dig_words + f.dig_off;
+                if (digests_on_device)
+                    P2_HIP(ctx, hipMemcpy2DAsync(dst, rounds.dig_words * 8, digests, nd * 32, nd * 32, g, hipMemcpyDeviceToDevice, ctx->stream));
+                else
+                    P2_TRY(d2h_2d(ctx, dst, rounds.dig_words * 8, digests, nd * 32, nd * 32, g));
+            }
+            if (caps_out) P2_TRY(d2h_2d(ctx, caps_out + (j0 * n_rounds + r) * cap_words, n_rounds * cap_words * 8, cap, cap_words * 8, cap_words * 8, g));
+            // prover.rs:106-109: observe_cap j, beta j
+            P2_TRY(challenger_many_dev(ctx, chs, g, cap, cap_words, cap_words, beta, 2, 2));
+            if (betas_out) P2_TRY(d2h_2d(ctx, betas_out + (j0 * n_rounds + r) * 2, n_rounds * 16, beta, 16, 16, g));
+            // prover.rs:111-118
+            const size_t out_n = cur_n >> ab;
+            P2HOT_LAUNCH(fri::fold_many_kernel, dim3(cdiv(out_n, 256), (unsigned)g), dim3(256), 0, ctx->stream, (const u64 *)cur, ab, (const u64 *)beta,
+                         out_n, nxt);
+            P2_LAUNCH_CHECK(ctx);
+            std::swap(cur, nxt);
+            cur_n = out_n;
+            log_cur -= ab;
+            m >>= ab;
+            shift = gl::pow(shift, (u64)1 << ab);
+        }
+        // prover.rs:122-132: the dummy zero caps, 4 zero elements per entry, and a challenge each
+        for (unsigned k = n_rounds; k < max_num_query_steps; ++k) P2_TRY(challenger_many_dev(ctx, chs, g, zeros, 0, cap_words, beta, 2, 2));
+        // prover.rs:135-139: the final polynomials, observed
+        P2HOT_LAUNCH(fri::interleave_many_kernel, dim3(cdiv(cur_n, 256), (unsigned)g), dim3(256), 0, ctx->stream, (const u64 *)cur, cur_n, stage,
+                     2 * cur_n);
+        P2_LAUNCH_CHECK(ctx);
+        P2_TRY(challenger_many_dev(ctx, chs, g, stage, 2 * cur_n, 2 * cur_n, nullptr, 0, 0));
+        if (final_out) P2_TRY(d2h(ctx, final_out + j0 * final_words, stage, g * cur_n * 16));
+        // prover.rs:140-147
+        for (size_t done = 0; done < extra;) {
+            const size_t chunk = std::min(extra - done, zero_words);
+            P2_TRY(challenger_many_dev(ctx, chs, g, zeros, 0, chunk, nullptr, 0, 0));
+            done += chunk;
+        }
+    }
+    return P2HOT_OK;
+}
+
+extern "C" int p2hot_fri_commit_many_dev(p2hot_ctx *ctx, size_t M, const uint64_t *d_coeffs_planar, unsigned log_n, unsigned rate_bits,
+                                         unsigned cap_height, const unsigned *arity_bits, unsigned n_rounds, unsigned max_num_query_steps,
+                                         size_t final_poly_coeff_len, p2hot_challenger *const *challengers, uint64_t *d_leaves_out,
+                                         uint64_t *digests_out, int digests_on_device, uint64_t *caps_out, uint64_t *betas_out,
+                                         uint64_t *final_out) {
+    if (!ctx) return P2HOT_EINVAL;
+    DeviceGuard dev_guard_(ctx);
+    if (M == 0) return P2HOT_OK;
+    // everything is checked before the first enqueue: a refused call leaves every transcript as it was
+    if (!d_coeffs_planar) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit_many: null coefficients");
+    if (n_rounds && !arity_bits) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit_many: null reduction_arity_bits");
+    if (n_rounds > 32) P2_FAIL(ctx, P2HOT_EINVAL, "fri_commit_many: more than 32 reduction rounds");
+    P2_TRY(check_log(ctx, log_n + rate_bits, "fri_commit_many"));
+    P2_TRY(challengers_many_check(ctx, "fri_commit_many", M, challengers));
+    {
+        FriRounds schedule;
+        P2_TRY(fri_rounds(ctx, "fri_commit_many", log_n, rate_bits, cap_height, arity_bits, n_rounds, &schedule));
+    }
+    PoolBuf scratch(ctx), d_tab(ctx);
+    std::vector<fri::Challenger *> tab(M);  // (lives until the synchronisation below: the host side of the table's upload)
+    for (size_t j = 0; j < M; ++j) tab[j] = challengers[j]->d;
+    auto body = [&]() -> int {
+        P2_TRY(pool_alloc(ctx, M * sizeof(fri::Challenger *), &d_tab.p));
+        P2_HIP(ctx, hipMemcpyAsync(d_tab.p, tab.data(), M * sizeof(fri::Challenger *), hipMemcpyHostToDevice, ctx->stream));
+        return fri_commit_many_core(ctx, M, d_coeffs_planar, log_n, rate_bits, cap_height, arity_bits, n_rounds, max_num_query_steps,
+                                    final_poly_coeff_len, (fri::Challenger *const *)d_tab.p, d_leaves_out, digests_out, digests_on_device != 0,
+                                    caps_out, betas_out, final_out, scratch);
+    };
+    int rc = body();
+    hipError_t e = stream_sync(ctx);  // host outputs are complete on return; the scratch block goes back to the cache idle
+    if (rc == P2HOT_OK && e != hipSuccess) P2_FAIL(ctx, P2HOT_EHIP, "fri_commit_many: %s", hipGetErrorString(e));
+    return rc;
+}
+
+// pow_search_dev for M transcripts: the same chunk schedule, every launch over all of them; d_best [M]
+static int pow_search_many_dev(p2hot_ctx *ctx, const fri::Challenger *const *d_chs, size_t M, unsigned pow_bits, unsigned long long *d_best,
+                               u64 *next_start) {
+    P2_HIP(ctx, hipMemsetAsync(d_best, 0xFF, 8 * M, ctx->stream));
+    int extra = 5;
+    if (const char *e = getenv("P2HOT_POW_RANGE_LOG")) extra = atoi(e);
+    const int lg = std::min((int)pow_bits + extra, 34);
+    const u64 limit = (u64)1 << (lg < 0 ? 0 : lg);
+    u64 chunk = (u64)1 << std::min(18u, std::max(14u, pow_bits)), start = 0;
+    while (start < limit) {
+        const u64 count = std::min(limit - start, chunk);
+        P2HOT_LAUNCH(fri::pow_many_kernel, dim3(cdiv(count, 256), (unsigned)M), dim3(256), 0, ctx->stream, d_chs, pow_bits, start, count, d_best);
+        P2_LAUNCH_CHECK(ctx);
+        start += count;
+        if (chunk < ((u64)1 << 24)) chunk <<= 1;
+    }
+    *next_start = start;
+    return P2HOT_OK;
+}
+
+extern "C" int p2hot_fri_pow_many(p2hot_ctx *ctx, size_t M, p2hot_challenger *const *challengers, unsigned pow_bits, uint64_t *witnesses_out) {
+    if (!ctx) return P2HOT_EINVAL;
+    DeviceGuard dev_guard_(ctx);
+    if (M == 0) return P2HOT_OK;
+    if (!witnesses_out) P2_FAIL(ctx, P2HOT_EINVAL, "fri_pow_many: null output");
+    if (pow_bits > 64) P2_FAIL(ctx, P2HOT_EINVAL, "fri_pow_many: pow_bits > 64");
+    if (M > 65535) P2_FAIL(ctx, P2HOT_EINVAL, "fri_pow_many: %zu transcripts exceed one launch (65535)", M);
+    P2_TRY(challengers_many_check(ctx, "fri_pow_many", M, challengers));
+    PoolBuf d_blk(ctx);  // transcript table [M] | best [M] | responses [M]
+    P2_TRY(pool_alloc(ctx, 3 * M * 8, &d_blk.p));
+    fri::Challenger **d_chs = reinterpret_cast<fri::Challenger **>(d_blk.u());
+    unsigned long long *d_best = reinterpret_cast<unsigned long long *>(d_blk.u() + M);
+    std::vector<fri::Challenger *> tab(M);
+    for (size_t j = 0; j < M; ++j) tab[j] = challengers[j]->d;
+    std::vector<unsigned long long> best(M, ~0ull);
+    auto body = [&]() -> int {
+        u64 next = 0;
+        P2_HIP(ctx, hipMemcpyAsync(d_chs, tab.data(), M * 8, hipMemcpyHostToDevice, ctx->stream));
+        P2_TRY(pow_search_many_dev(ctx, d_chs, M, pow_bits, d_best, &next));
+        P2_HIP(ctx, hipMemcpyAsync(best.data(), d_best, M * 8, hipMemcpyDeviceToHost, ctx->stream));
+        P2_HIP(ctx, stream_sync(ctx));
+        // no witness in the device-searched range (probability e^-32 each): that transcript alone continues with host-checked
+        // chunks (the grind reads the transcript and leaves it as it was, so nothing is rewound); d_best[j] ends as its witness
+        for (size_t j = 0; j < M; ++j)
+            if (best[j] == ~0ull) P2_TRY(pow_continue_host(ctx, challengers[j], pow_bits, d_best + j, next, &best[j]));
+        // prover.rs:197-198: observe witness j, draw response j
+        P2_TRY(challenger_many_dev(ctx, d_chs, M, (const u64 *)d_best, 1, 1, d_blk.u() + 2 * M, 1, 1));
+        return P2HOT_OK;
+    };
+    int rc = body();
+    hipError_t e = stream_sync(ctx);
+    if (rc == P2HOT_OK && e != hipSuccess) P2_FAIL(ctx, P2HOT_EHIP, "fri_pow_many: %s", hipGetErrorString(e));
+    if (rc == P2HOT_OK)
+        for (size_t j = 0; j < M; ++j) witnesses_out[j] = best[j];
+    return rc;
 }
 
 // ------------------------------------------------------------------ PolynomialBatch, host pointers

@@ -35,6 +35,7 @@ ROWS = [
     ("f6", "a STARK's own constraints from a constraint program: the consumer's accumulators, the table's whole quotient", "test_stark_air.py (the builder; the accumulators point by point vs tests/stark_air_ref.py, constraint functions restated from starky's fibonacci_stark.rs and a synthetic AIR, plus an independent interpreter of the program format; fused = two-step bit for bit; FibonacciStark's quotient through verifier.rs:167-186 at an extension point; divisibility; the temp cap; every error), test_stark_air_codeobj.py, test_edge_words.py (a program whose temps leave [0, P), on edge traces)", None),
     ("f7", "user-defined gates' constraints from gate programs: the reduced sums, the plonk quotient with and without lookups", "test_gate_program.py (the builder; nine reference gates transcribed for it vs the hand-written kinds and tests/gates_ref.py bit for bit; a gate the library does not know vs tests/gate_program_ref.py, an independent interpreter of the format, and vs a plain function; a mixed call vs the reference sum and vs the host residual; the device quotient through verifier.rs:83-98; a broken wire; every error; Keccak-hashed commitments), test_gate_program_codeobj.py, test_edge_words.py (a program whose temps leave [0, P), on edge rows)", None),
     ("f8", "the middle of a proof for M witnesses of one circuit: partial products and Zs, commitment of interleaved device columns, quotient with gate constraints, OpeningSet", "test_many_middle.py (every M-form vs M single-proof calls word for word: handles sharing one block and separately committed ones, one and two scan chunks, the pipelined and the generic quotient instantiation, per-proof challenges and public-inputs hashes; one proof's chunks through verifier.rs:83-98; a zero denominator and a broken wire name their proof; the whole chain for M = 4 up to the opening proofs' bytes; every argument error), test_many_middle_codeobj.py, test_edge_words.py (an edge proof between two random ones)", None),
+    ("f9", "opening proofs of M proofs of one shape in one set of launches: final polynomials, commit phase (one forest per round), grind, query rounds", "test_fri_many.py (p2hot_fri_commit_many_dev, p2hot_fri_pow_many and the fused p2hot_prove_openings_many vs M single calls word for word, transcripts included: differently filled transcripts, shared-block / separate / salted oracles, degenerate geometry, two groups, a grind miss beside hits, the fallback, one proof through oracle/fri_verifier.py, every error before any work), test_fri_many_edge_words.py (fold, final-poly and transcript M-forms on edge words vs Python integers), test_fri_many_codeobj.py; profiles/prove_openings_many.json", None),
     ("g1", "patched CircuitBuilder::build / prove vs the Rust prover", "integration/first_contact.sh (dry-run only: no cargo in the image)", None),
 ]
 
